@@ -18,6 +18,11 @@ sessions, its peers follow the leader's scheduler iterations in lockstep); the r
 over ALL sessions of all ranks / groups.
 
 Data: synthetic speech-like audio, random-init weights of the named architectures.
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the
+result line.  `--dump-outputs DIR` also writes what the last timed step returned to its caller
+(transcript and intent, see `dump_outputs`).  Every further measurement (today the concurrent
+sessions of `--concurrent`) runs only with `--full`.
 """
 from __future__ import annotations
 
@@ -154,6 +159,18 @@ def run_concurrent(args, C, asr, brain, utterances, asr_tokens, world, tp):
                              for k, v in getattr(brain, "timing", {}).items()}}
 
 
+def dump_outputs(path: str, text: str, out) -> None:
+    """What the last timed step handed to its caller, as float32 arrays under ``path``:
+    ``transcript_utf8.npy`` (the ASR transcript's UTF-8 bytes) and ``intent_json_utf8.npy`` (the
+    UTF-8 bytes of the validated intent object, keys sorted).  The utterances, weights and sampler
+    seed are fixed, so two builds given the same arguments are comparable array for array."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"transcript_utf8": text.encode("utf-8"),
+              "intent_json_utf8": json.dumps(out, sort_keys=True, ensure_ascii=False).encode("utf-8")}
+    for name, raw in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.frombuffer(raw, dtype=np.uint8).astype(np.float32))
+
+
 def _free_port() -> int:
     import socket
 
@@ -194,9 +211,14 @@ def main():
     ap.add_argument("--asr-tokens-per-s", type=float, default=4.0)
     ap.add_argument("--budget-chars", type=int, default=512)
     ap.add_argument("--debounce-ms", type=float, default=1000.0, help="reference debounce added for parity_p50_ms")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (--concurrent); a run without it "
+                         "sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's transcript and intent to DIR/<name>.npy")
     ap.add_argument("--concurrent", type=int, default=knob("VWA_BENCH_CONCURRENT"),
-                    help="also measure C concurrent voice sessions per rank (batched ASR + continuous-batched "
-                         "intent decoding); reported under 'concurrent', outside the headline value")
+                    help="with --full: also measure C concurrent voice sessions per rank (batched ASR + continuous-"
+                         "batched intent decoding); reported under 'concurrent', outside the headline value")
     ap.add_argument("--dtype", default=knob("VWA_DTYPE"), choices=("bf16", "fp8"),
                     help="LLM weight dtype: bf16 (headline config) or fp8 (W8A8 on the fp8 MFMA, config 5)")
     ap.add_argument("--no-graphs", action="store_true")
@@ -225,7 +247,9 @@ def main():
     t_load = time.time()
     wcfg, lcfg = get_config(args.asr), get_config(args.llm)
     whisper = WhisperModel(wcfg, device=dev, seed=1)
-    C = max(0, args.concurrent)
+    C = max(0, args.concurrent) if args.full else 0
+    if args.concurrent > 1 and not args.full and rank == 0:
+        print(f"bench.py: --concurrent {args.concurrent} is measured only with --full; not run", file=sys.stderr)
     asr = AsrEngine(whisper, load_tokenizer("whisper"), max_sessions=max(2, C), use_graphs=use_graphs)
     llama = LlamaModel(lcfg, device=dev, tp=tp, seed=2, wdtype=args.dtype)
     engine = LLMEngine(llama, max_seqs=max(4, C), max_model_len=2048, use_graphs=use_graphs)
@@ -279,6 +303,8 @@ def main():
     llm_stats = [r[3] for r in res_steps]
     n_it = max(1, brain.batch_stats["iterations"] - it0)
     host_us = {k.replace("_ms", "_us"): round((brain.timing[k] - tm0[k]) * 1e3 / n_it, 1) for k in tm0}
+    if args.dump_outputs and rank == 0 and "out" in last:
+        dump_outputs(args.dump_outputs, last["text"], last["out"])
 
     conc = run_concurrent(args, C, asr, brain, utterances, asr_tokens, world, tp) if C > 1 else None
 

@@ -30,3 +30,26 @@ def test_bench_refuses_world_size_mismatch():
 def test_bench_needs_a_gpu():
     r = _run(["--steps", "1", "--warmup", "0"])
     assert r.returncode != 0 and "needs a GPU" in (r.stdout + r.stderr)
+
+
+def test_bench_full_and_dump_outputs_are_accepted():
+    """--full and --dump-outputs parse (the run then stops where every GPU-less run stops)."""
+    r = _run(["--steps", "1", "--warmup", "0", "--full", "--dump-outputs", "unused"])
+    assert r.returncode != 0 and "needs a GPU" in (r.stdout + r.stderr)
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    import json
+
+    import numpy as np
+
+    import bench  # (tests/conftest.py puts the repository root on sys.path)
+
+    out = {"version": "1.0", "intents": [{"type": "search", "args": {"query": "café"}}], "confidence": 0.5}
+    d = tmp_path / "dump"
+    bench.dump_outputs(str(d), "search café", out)
+    assert sorted(p.name for p in d.iterdir()) == ["intent_json_utf8.npy", "transcript_utf8.npy"]
+    t, j = np.load(d / "transcript_utf8.npy"), np.load(d / "intent_json_utf8.npy")
+    assert t.dtype == np.float32 and j.dtype == np.float32
+    assert bytes(t.astype(np.uint8)).decode("utf-8") == "search café"
+    assert json.loads(bytes(j.astype(np.uint8)).decode("utf-8")) == out

@@ -35,8 +35,8 @@ for r in "$@"; do
     tests) add gpu_tests 1200 "$PT tests" ;;
     bench)
       add bench_bf16 400 "python -u bench.py"
-      add bench_bf16_c8 500 "python -u bench.py --concurrent 8 --steps 10 --warmup 3"
-      add bench_fp8_c32 600 "python -u bench.py --dtype fp8 --concurrent 32 --steps 10 --warmup 3" ;;
+      add bench_bf16_c8 500 "python -u bench.py --full --concurrent 8 --steps 10 --warmup 3"
+      add bench_fp8_c32 600 "python -u bench.py --full --dtype fp8 --concurrent 32 --steps 10 --warmup 3" ;;
     prof) add prof_bf16 400 "rocprofv3 --kernel-trace --stats -d gpurun_out/prof_bf16 -o run -- python3 -u bench.py --steps 5 --warmup 2" ;;
     pmc)
       pmc3 pmc_kernels tools/pmc_kernels.py

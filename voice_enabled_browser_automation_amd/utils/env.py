@@ -148,7 +148,7 @@ class Settings(BaseModel):
     VWA_ATTN_IMPL: Optional[str] = Field(None, description="DIAGNOSTIC: decode attention implementation")
     VWA_KERNEL_SO: Optional[str] = Field(None, description="DIAGNOSTIC: another build of the kernel library (A/B)")
     VWA_STRICT_NATIVE: bool = Field(False, description="vendor-library fallbacks in the op layer raise (tests, bench)")
-    VWA_BENCH_CONCURRENT: int = Field(0, description="bench.py: concurrent sessions (0: the single-session headline)")
+    VWA_BENCH_CONCURRENT: int = Field(0, description="bench.py --full: concurrent sessions (0: the headline only)")
     # ---- build
     VWA_FORCE_BUILD: bool = Field(False, description="__graft_entry__.build(): recompile every source")
     VWA_HIPCC_EXTRA: str = Field("", description="extra hipcc flags (experiments)")
