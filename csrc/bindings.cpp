@@ -1337,7 +1337,7 @@ void pcm16_to_f32(Tensor pcm, Tensor out, double ratio) {
   check_vec(out, pcm, at::kFloat, 0, "out");
   const int n_in = (int)pcm.numel(), n_out = (int)out.numel();
   TORCH_CHECK((int64_t)((n_out - 1) * ratio) < (int64_t)n_in + 1, "resample ratio overruns input");
-  check_rc(vwa_pcm16_to_f32(pcm.data_ptr<int16_t>(), out.data_ptr<float>(), n_in, n_out, (float)ratio, cur_stream(pcm)),
+  check_rc(vwa_pcm16_to_f32(pcm.data_ptr<int16_t>(), out.data_ptr<float>(), n_in, n_out, ratio, cur_stream(pcm)),
            "pcm16_to_f32");
 }
 

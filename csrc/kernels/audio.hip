@@ -18,16 +18,18 @@ namespace {
 constexpr int kNFFT = 400, kHop = 160, kBins = 201;
 
 __global__ __launch_bounds__(256) void pcm_kernel(const int16_t* __restrict__ pcm, float* __restrict__ out, int n_in,
-                                                  int n_out, float ratio) {
+                                                  int n_out, double ratio) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_out) return;
-  if (ratio == 1.f) {
+  if (ratio == 1.0) {
     out[i] = (float)pcm[i] * (1.f / 32768.f);
     return;
   }
-  const float src = i * ratio;
+  // read position in f64: an f32 product drifts by up to 0.1 sample over a 30 s window at 44.1 kHz
+  // (480 000 outputs x a ratio that is no dyadic fraction needs more than 24 bits)
+  const double src = (double)i * ratio;
   int j = (int)src;
-  const float f = src - j;
+  const float f = (float)(src - (double)j);
   const int j1 = min(j + 1, n_in - 1);
   j = min(j, n_in - 1);
   out[i] = ((1.f - f) * pcm[j] + f * pcm[j1]) * (1.f / 32768.f);
@@ -208,7 +210,7 @@ __global__ __launch_bounds__(256) void logmel_norm_kernel(const float* __restric
 
 }  // namespace
 
-extern "C" int vwa_pcm16_to_f32(const int16_t* pcm, float* out, int n_in, int n_out, float ratio, hipStream_t st) {
+extern "C" int vwa_pcm16_to_f32(const int16_t* pcm, float* out, int n_in, int n_out, double ratio, hipStream_t st) {
   hipLaunchKernelGGL(pcm_kernel, dim3((n_out + 255) / 256), dim3(256), 0, st, pcm, out, n_in, n_out, ratio);
   return (int)hipGetLastError();
 }

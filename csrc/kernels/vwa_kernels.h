@@ -289,7 +289,7 @@ int vwa_sample_partial(const float* logits, int ld, int rows, int V, int v_off, 
                        int* part_idx, int n_chunks, hipStream_t st);
 int vwa_sample_final(const float* part_val, const int* part_idx, int n_chunks, int n_src, int64_t src_stride,
                      int* out_tokens, int* step, int rows, const int64_t* fail_word, hipStream_t st);
-int vwa_pcm16_to_f32(const int16_t* pcm, float* out, int n_in, int n_out, float ratio, hipStream_t st);
+int vwa_pcm16_to_f32(const int16_t* pcm, float* out, int n_in, int n_out, double ratio, hipStream_t st);
 // basis: DFT cos/sin fragments [26 tiles][25][64][4] f32, fb_frag: mel filterbank fragments
 // [n_mels/16][13][64][4] f32 (ops.logmel_tables)
 int vwa_log_mel(const float* audio, int n_samples, int n_frames, const float* window, const float* basis,
