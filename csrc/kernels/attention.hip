@@ -33,7 +33,8 @@ constexpr int kKeysPerWave = 64;
 constexpr int kSplit = kWaves * kKeysPerWave;  // keys per decode workgroup (chunk)
 
 
-// One 4-wave workgroup per (row, kv head, 256-key chunk); each wave owns 64 keys.
+// One 4-wave workgroup per (row, kv head, chunk of 256-key passes -- one pass unless n_splits caps the
+// chunks); each wave owns 64 keys of a pass.
 //  Q.K: lane = key, the key row streamed with D/8 independent 16-byte loads (V loads issued
 //  right behind them: their addresses do not depend on the scores).  P.V: lane = (16-byte dim
 //  chunk, token group), token groups reduced with xor-shuffles.  The 4 waves' (m, l, o) are
@@ -59,86 +60,116 @@ __global__ __launch_bounds__(kWaves * 64) void decode_attn_kernel(DecodeAttnPara
   const int chunk = blockIdx.y;
   const int ctx = p.ctx_lens[row];
   const int seq = p.seq_ids[row];
-  if (chunk * kSplit >= ctx) return;  // chunk past this row's context (grid sized for max_ctx)
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int t0 = chunk * kSplit + w * kKeysPerWave;
-  const int tend = min(ctx, t0 + kKeysPerWave);  // t0 >= tend: this wave has no keys
-  const int nact = (ctx + kSplit - 1) / kSplit;  // active chunks of this row
-
-  // ---- issue K (lane = key) and V (lane = chunk c, token group tg) loads first
+  if (ctx == 0) {  // no key: the row's output is zeros (DecodeAttnParams::out), written by chunk 0
+    if (chunk == 0)
+      for (int i = threadIdx.x; i < G * D; i += kWaves * 64) p.out[(int64_t)row * p.ldo + kvh * G * D + i] = 0;
+    return;
+  }
+  // The row's 256-key passes are dealt out over at most n_splits chunks (grid.y, the partial slots
+  // a row has): one pass per chunk unless n_splits caps them -- then a chunk walks `ppc` passes
+  // with an online softmax per wave (n_splits = 1: one chunk, written directly, no partials).
+  const int npass = (ctx + kSplit - 1) / kSplit;
+  const int ppc = (npass + p.n_splits - 1) / p.n_splits;
+  const int nact = (npass + ppc - 1) / ppc;  // active chunks of this row
+  if (chunk >= nact) return;  // chunk past this row's context (grid sized for max_ctx)
   const int c = lane % NCH, tg = lane / NCH;
-  const int t = t0 + lane;
-  uint4 kv4[NCH];
-  if (t < tend) {
-    const uint4* kr = reinterpret_cast<const uint4*>(p.kv.k + kv_offset(p.kv, seq, kvh, t));
-#pragma unroll
-    for (int cc = 0; cc < NCH; ++cc) kv4[cc] = kr[cc];
-  }
-  uint4 vv[NI];
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int tt = t0 + tg + TG * i;
-    vv[i] = (tt < tend) ? *reinterpret_cast<const uint4*>(p.kv.v + kv_offset(p.kv, seq, kvh, tt) + c * 8)
-                        : make_uint4(0, 0, 0, 0);
-  }
-  // q (scaled) into LDS while the K/V loads are in flight
-  for (int i = threadIdx.x * 8; i < G * D; i += kWaves * 64 * 8) {
-    const int g = i / D, d = i % D;
-    float f[8];
-    unpack8(*reinterpret_cast<const uint4*>(p.q + (int64_t)row * p.ldq + (kvh * G + g) * D + d), f);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) qs[g][d + j] = f[j] * p.scale;
-  }
-  __syncthreads();
 
-  // ---- Q.K and the wave's softmax statistics
-  float s[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) s[g] = 0.f;
-  if (t < tend) {
-#pragma unroll
-    for (int cc = 0; cc < NCH; ++cc) {
-      float kf[8];
-      unpack8(kv4[cc], kf);
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const float4 qa = *reinterpret_cast<const float4*>(&qs[g][cc * 8]);
-        const float4 qb = *reinterpret_cast<const float4*>(&qs[g][cc * 8 + 4]);
-        s[g] += qa.x * kf[0] + qa.y * kf[1] + qa.z * kf[2] + qa.w * kf[3] + qb.x * kf[4] + qb.y * kf[5] +
-                qb.z * kf[6] + qb.w * kf[7];
-      }
-    }
-  }
+  float mrun[G], lrun[G], o[G][8];
 #pragma unroll
   for (int g = 0; g < G; ++g) {
-    const float v = (t < tend) ? s[g] : -INFINITY;
-    const float m = wave_max(v);
-    const float e = (t < tend) ? __expf(v - m) : 0.f;
-    const float l = wave_sum(e);
-    sc[w][g][lane] = e;
-    if (lane == 0) {
-      mlw[w][g][0] = m;  // -inf for a wave without keys
-      mlw[w][g][1] = l;
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-
-  // ---- P.V (V already in registers)
-  float o[G][8];
-#pragma unroll
-  for (int g = 0; g < G; ++g)
+    mrun[g] = -INFINITY;
+    lrun[g] = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[g][j] = 0.f;
+  }
+  for (int ps = 0; ps < ppc; ++ps) {
+    const int t0 = (chunk * ppc + ps) * kSplit + w * kKeysPerWave;
+    const int tend = min(ctx, t0 + kKeysPerWave);  // t0 >= tend: this wave has no keys in this pass
+
+    // ---- issue K (lane = key) and V (lane = chunk c, token group tg) loads first
+    const int t = t0 + lane;
+    uint4 kv4[NCH];
+    if (t < tend) {
+      const uint4* kr = reinterpret_cast<const uint4*>(p.kv.k + kv_offset(p.kv, seq, kvh, t));
 #pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    float vf[8];
-    unpack8(vv[i], vf);
+      for (int cc = 0; cc < NCH; ++cc) kv4[cc] = kr[cc];
+    }
+    uint4 vv[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const int tt = t0 + tg + TG * i;
+      vv[i] = (tt < tend) ? *reinterpret_cast<const uint4*>(p.kv.v + kv_offset(p.kv, seq, kvh, tt) + c * 8)
+                          : make_uint4(0, 0, 0, 0);
+    }
+    if (ps == 0) {
+      // q (scaled) into LDS while the first pass's K/V loads are in flight
+      for (int i = threadIdx.x * 8; i < G * D; i += kWaves * 64 * 8) {
+        const int g = i / D, d = i % D;
+        float f[8];
+        unpack8(*reinterpret_cast<const uint4*>(p.q + (int64_t)row * p.ldq + (kvh * G + g) * D + d), f);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qs[g][d + j] = f[j] * p.scale;
+      }
+      __syncthreads();
+    }
+
+    // ---- Q.K and the wave's softmax statistics (running over the chunk's passes)
+    float s[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) s[g] = 0.f;
+    if (t < tend) {
+#pragma unroll
+      for (int cc = 0; cc < NCH; ++cc) {
+        float kf[8];
+        unpack8(kv4[cc], kf);
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const float4 qa = *reinterpret_cast<const float4*>(&qs[g][cc * 8]);
+          const float4 qb = *reinterpret_cast<const float4*>(&qs[g][cc * 8 + 4]);
+          s[g] += qa.x * kf[0] + qa.y * kf[1] + qa.z * kf[2] + qa.w * kf[3] + qb.x * kf[4] + qb.y * kf[5] +
+                  qb.z * kf[6] + qb.w * kf[7];
+        }
+      }
+    }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-      const float pg = sc[w][g][tg + TG * i];
+      const float v = (t < tend) ? s[g] : -INFINITY;
+      const float m = fmaxf(mrun[g], wave_max(v));  // -inf while the wave has seen no key
+      const float e = (t < tend) ? __expf(v - m) : 0.f;
+      const float l = wave_sum(e);
+      sc[w][g][lane] = e;
+      if (ps > 0) {  // (the first pass starts from zeros: nothing to rescale)
+        const float alpha = (mrun[g] == -INFINITY) ? 0.f : __expf(mrun[g] - m);
+        lrun[g] *= alpha;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) o[g][j] += pg * vf[j];
+        for (int j = 0; j < 8; ++j) o[g][j] *= alpha;
+      }
+      lrun[g] += l;
+      mrun[g] = m;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+
+    // ---- P.V (V already in registers)
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      float vf[8];
+      unpack8(vv[i], vf);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const float pg = sc[w][g][tg + TG * i];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[g][j] += pg * vf[j];
+      }
+    }
+    __builtin_amdgcn_wave_barrier();  // the next pass overwrites sc[w]
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      mlw[w][g][0] = mrun[g];  // -inf for a wave without keys
+      mlw[w][g][1] = lrun[g];
     }
   }
 #pragma unroll

@@ -373,6 +373,17 @@ VWA_DEVICE bool mq_body(const DecodeAttnParams& p, unsigned char* lds, int grid,
     kbeg = chunk * CL;
     if (kbeg >= ctxmax) {
       if (item == bid) write_plan(2, 0, 0, 0, 0, 0, 0, 0, 0);
+      if constexpr (!FINE) {
+        // a group whose rows all have ctx_len == 0 has no key step that would store anything: its
+        // chunk-0 item writes the zeros (DecodeAttnParams::out; a zero-context row beside live rows
+        // of its group gets them from the merge, l == 0)
+        if (ctxmax == 0 && chunk == 0) {
+          const int zn = VWA_TX >> 4, zc = VWA_TX & 15;
+          if (zn < kMqCols && zn / G < nr && zc < NCH)
+            store_out<SC1OUT>(p.out + (int64_t)(r0 + zn / G) * p.ldo + (kvh * G + zn % G) * D + 8 * zc,
+                              make_uint4(0, 0, 0, 0));
+        }
+      }
       continue;
     }
     kend = min(ctxmax, kbeg + CL);

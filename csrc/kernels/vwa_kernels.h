@@ -57,10 +57,14 @@ struct DecodeAttnParams {
   int rows, n_q_heads, n_kv_heads, head_dim;
   float scale;
   int split_tokens;                 // keys per split workgroup
-  int n_splits;                     // max splits (grid.y)
+  int n_splits;                     // max key chunks (partial slots) per row, both kernels honour it; 1: no partials
   float* part_o; float* part_ml;    // [rows][n_splits][n_q_heads][D], [rows][n_splits][n_q_heads][2]
   int* counters;                    // [rows * n_kv_heads] chunk tickets, zero between launches
-  uint16_t* out; int ldo;           // [rows, n_q_heads*D]
+  // [rows, n_q_heads*D]; every row is written by the standalone kernels (decode_mq_kernel,
+  // decode_attn_kernel): a row with ctx_lens == 0 has no key and gets zeros, as ops/reference.py
+  // writes them.  (The chained launch's attention phase requires ctx_lens >= 1: the engines pad
+  // with one key, and a group without keys stores nothing there.)
+  uint16_t* out; int ldo;
   // optional (chained attention, <= 4 rows): the block table of each ROW's sequence, [rows][rt_stride
   // <= 128] -- read in the same round trip as seq_ids / ctx_lens (no dependent table load)
   const int* row_table; int rt_stride;
