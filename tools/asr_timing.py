@@ -2,6 +2,7 @@
 launches (models/whisper.py, skinny_stream.hip chain_kernel SEQ 1/2), fixed 40-token work on the
 bench's synthetic 10 s utterance.  One JSON line per mode.
 python tools/asr_timing.py [--asr whisper-large-v3] [--reps 10]
+python tools/asr_timing.py --words [--asr whisper-large-v3]   # the final pass without / with word timestamps
 
 decode_us_per_token = host time from the encoder's launch to the last token / tokens (includes the
 encoder and cross K/V projections still running after their launch); decode_gpu_us_per_token = the
@@ -33,6 +34,8 @@ def main():
     ap.add_argument("--modes", default="0,p",
                     help="decoder forms to time: 0 per-kernel, 1 chained launches (VWA_CHAIN_ASR), p the persistent "
                          "one-launch decoder (VWA_ASR_PERSIST, whisper-large)")
+    ap.add_argument("--words", action="store_true",
+                    help="time the final pass without and with word timestamps (the alignment pass after the decode)")
     ap.add_argument("--small-max-m", type=int, default=None,
                     help="A/B: rows up to which small weights take the one-tile kernel (16: the tiled GEMM above 16)")
     a = ap.parse_args()
@@ -59,6 +62,28 @@ def main():
             print(json.dumps(dict(tool="asr_timing", asr=a.asr, batch=B, tokens=a.tokens,
                                   total_ms=round(statistics.median(ts), 2), encode_ms=round(statistics.median(enc), 2),
                                   decode_ms=round(statistics.median(dec), 2))), flush=True)
+        return
+    if a.words:  # the final pass with and without the word-alignment pass (decode_many(words=True))
+        eng = AsrEngine(m, load_tokenizer("whisper"), max_sessions=2)
+        audio = eng.pcm_to_audio(synth_speech(10.0, seed=100))
+        toks = {}
+        for on in (False, True, False, True):  # interleaved: off / on / off / on, reps each
+            for _ in range(2):
+                eng.decode_many([audio], exact_tokens=a.tokens, words=on)
+            tot, al = [], []
+            for _ in range(a.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                toks.setdefault(on, eng.decode_many([audio], exact_tokens=a.tokens, words=on)[0])
+                tot.append((time.perf_counter() - t0) * 1e3)
+                al.append(eng.last_stats.get("align_ms", 0.0))
+            q = statistics.quantiles(tot, n=4) if len(tot) >= 4 else [min(tot), statistics.median(tot), max(tot)]
+            print(json.dumps(dict(tool="asr_timing", asr=a.asr, words=on, tokens=a.tokens, reps=a.reps,
+                                  total_ms=round(statistics.median(tot), 3), total_ms_min=round(min(tot), 3),
+                                  total_ms_max=round(max(tot), 3), total_ms_q1=round(q[0], 3),
+                                  total_ms_q3=round(q[2], 3), align_ms=round(statistics.median(al), 3),
+                                  align_heads=m.align_layers()[1])), flush=True)
+        print(json.dumps(dict(tool="asr_timing", asr=a.asr, same_tokens=toks[False] == toks[True])), flush=True)
         return
     audio = None
     texts = {}

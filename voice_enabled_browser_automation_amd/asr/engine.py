@@ -17,6 +17,7 @@ import torch
 
 from .. import ops
 from ..models.whisper import WhisperModel
+from .words import Alignment, group_words
 
 BUCKETS = (1, 2, 4, 8, 16, 32, 64)
 
@@ -115,8 +116,10 @@ class WhisperRunner:
         self.graphs[M] = (g, out)
         return self.graphs[M]
 
-    def step(self, rows: Sequence[Tuple[int, int, int]]) -> torch.Tensor:
-        """rows: (session slot, token, position). Returns f32 logits [len(rows), vocab_padded]."""
+    def step(self, rows: Sequence[Tuple[int, int, int]], fwd=None) -> torch.Tensor:
+        """rows: (session slot, token, position). Returns f32 logits [len(rows), vocab_padded].
+        ``fwd``: the forward to run on the staged rows instead of the (graph-replayed) decode step --
+        ``fwd(M) -> logits`` (the word-alignment pass, never captured)."""
         n = len(rows)
         M = next(bk for bk in BUCKETS if bk >= n)
         if self._copy_done is not None:
@@ -139,7 +142,9 @@ class WhisperRunner:
             if self._copy_done is None:
                 self._copy_done = torch.cuda.Event()
             self._copy_done.record()
-        if self.use_graphs:
+        if fwd is not None:
+            out = fwd(M)
+        elif self.use_graphs:
             g, out = self.graphs.get(M) or self._capture(M)
             g.replay()
         else:
@@ -174,6 +179,8 @@ class AsrEngine:
         self.loop_graphs: Dict[Tuple[int, bool, int], torch.cuda.CUDAGraph] = {}
         self.device_loop = self.runner.use_graphs and ops.env_flag("VWA_ASR_DEVICE_LOOP")
         self.last_stats: Dict[str, float] = {}
+        # decode_many(words=True): one entry per utterance of the last call (asr/words.py Alignment)
+        self.last_alignments: List[Alignment] = []
         self.free_slots = list(range(max_sessions - 1, -1, -1))
 
     @staticmethod
@@ -318,12 +325,18 @@ class AsrEngine:
         return max(0, r.bps * r.bs - len(self.prompt) - 1)
 
     def decode_many(self, audios: List[torch.Tensor], prefixes: Optional[Sequence[Sequence[int]]] = None, *,
-                    max_tokens: int = 96, min_tokens: int = 0, exact_tokens: Optional[int] = None) -> List[List[int]]:
+                    max_tokens: int = 96, min_tokens: int = 0, exact_tokens: Optional[int] = None,
+                    words: bool = False) -> List[List[int]]:
         """Token ids decoded for each utterance.  ``prefixes[i]``: text tokens forced after the
         SOT sequence (a streaming session's committed transcript -- asr/streaming.py local
         agreement): they are prefilled in the same ragged prompt step as the SOT tokens and only
         the continuation is decoded; the result EXCLUDES the prefix.  A prefix longer than
-        ``max_prefix()`` is cut to that length (callers build hypotheses from the cut prefix)."""
+        ``max_prefix()`` is cut to that length (callers build hypotheses from the cut prefix).
+
+        ``words``: also align the transcript (prefix + decoded tokens) to the audio and score its
+        tokens, before the session slots are released -- ``self.last_alignments[i]`` then holds
+        utterance i's token ids, first / last 20 ms frame per token and token log-probabilities
+        (``_align``).  Off: nothing is allocated or launched for it."""
         t0 = time.perf_counter()
         m = self.model
         B = len(audios)
@@ -384,11 +397,114 @@ class AsrEngine:
                                    tokens=sum(len(o) for o in outs), batch=B,
                                    prefix_tokens=sum(len(p) - len(self.prompt) for p in prompts))
             if not retry:
+                if words:
+                    self.last_alignments = self._align(slots, audios, prompts, outs, exact_tokens is not None,
+                                                       min_tokens)
+                    self.last_stats["align_ms"] = (time.perf_counter() - t_end) * 1e3
                 return outs
         finally:
             self.free_slots.extend(slots)
         return self.decode_many(audios, prefixes, max_tokens=max_tokens, min_tokens=min_tokens,
-                                exact_tokens=exact_tokens)
+                                exact_tokens=exact_tokens, words=words)
+
+    keep_costs = False  # _align: also keep each utterance's cost matrix (host copy) in its Alignment
+
+    def _align(self, slots: List[int], audios: List[torch.Tensor], prompts: List[List[int]], outs: List[List[int]],
+               exact: bool, min_tokens: int) -> List[Alignment]:
+        """Word alignment and token scores of every session, while it still holds its slot:
+
+        1. a teacher-forced decoder pass over SOT prompt + forced prefix + decoded tokens (<= 64 rows
+           per step, a session's rows in order) that records the alignment heads' cross-attention
+           probabilities over the audio's frames (models/whisper.py align_step) and scores each
+           step's logits (row p scores token p + 1, under the mask the sampler used there);
+        2. per session the alignment cost over its text-token rows and the DTW path;
+        3. ONE device -> host copy of every session's frames and log-probabilities."""
+        m = self.model
+        cfg = m.cfg
+        dev = m.device
+        r = self.runner
+        R = max(BUCKETS)
+        S = cfg.n_audio_ctx
+        P0 = len(self.prompt)
+        n_heads = m.align_layers()[1]
+        seqs = [p + o for p, o in zip(prompts, outs)]
+        n_keys = [min(S, max(1, -(-int(a.numel()) // 320))) for a in audios]
+        n_text = [len(s) - P0 for s in seqs]
+        live = [i for i in range(len(seqs)) if n_text[i] > 0]
+        result = [Alignment(n_keys=n_keys[i]) for i in range(len(seqs))]
+        if not live:
+            return result
+        rows: List[Tuple[int, int, int]] = []   # (slot, token, position) of every row, session by session
+        owner: List[int] = []                   # the row's session
+        targets: List[int] = []
+        sel: List[int] = []                     # 0: text ids only, 1: text ids + EOT (the sampler's two masks)
+        base: Dict[int, int] = {}
+        for i in live:
+            base[i] = len(rows)
+            seq = seqs[i]
+            for p, t in enumerate(seq):
+                rows.append((slots[i], t, p))
+                owner.append(i)
+                scored = P0 - 1 <= p < len(seq) - 1
+                tgt = seq[p + 1] if scored else 0
+                k = p + 1 - len(prompts[i])     # index among the decoded tokens (< 0: forced prefix)
+                only_text = exact or 0 <= k < min_tokens
+                if scored and not (0 <= tgt < cfg.eot):
+                    raise ValueError(f"token {tgt} of utterance {i} is not a text token: the sampler's mask forbids it")
+                targets.append(tgt)
+                sel.append(0 if only_text else 1)
+        G = len(rows)
+        n_tot = sum(n_text[i] for i in live)
+        host = torch.tensor(targets + sel, dtype=torch.int32)
+        d_in = host.to(dev)
+        tgt_d, sel_d = d_in[:G], d_in[G:]
+        masks = (self.mask_text, self.mask_text_eot)
+        uniform = masks[sel[0]] if len(set(sel)) == 1 else None
+        both = None if uniform is not None else torch.cat(masks)
+        # frames and log-probabilities of every session in one buffer: [first | last | log-prob bits]
+        res = torch.zeros(2 * n_tot + G, dtype=torch.int32, device=dev)
+        lp = res[2 * n_tot :].view(torch.float32)
+        probs = {i: torch.empty(n_heads, len(seqs[i]), S, dtype=torch.float32, device=dev) for i in live}
+        for g0 in range(0, G, R):
+            g1 = min(G, g0 + R)
+            segs = []
+            a = g0
+            while a < g1:
+                i = owner[a]
+                e = a
+                while e < g1 and owner[e] == i:
+                    e += 1
+                segs.append((a - g0, e - a, slots[i], probs[i], rows[a][2], n_keys[i]))
+                a = e
+            logits = r.step(rows[g0:g1], fwd=lambda M, segs=segs: m.align_step(r.b, M, segs))
+            mask = uniform if uniform is not None else both[sel_d[g0:g1].long()]
+            ops.token_logprob(logits, tgt_d[g0:g1], mask, cfg.vocab_size, out=lp[g0:g1])
+        off = {}
+        o = 0
+        costs = {}
+        for i in live:
+            n = n_text[i]
+            cost = ops.align_cost(probs[i][:, P0:], n, n_keys[i])
+            ops.dtw_path(cost, n, n_keys[i], res[o : o + n], res[n_tot + o : n_tot + o + n])
+            if self.keep_costs:
+                costs[i] = cost[:n, : n_keys[i]]
+            off[i] = o
+            o += n
+        h = res.cpu()  # the one copy (it also waits for the pass)
+        h_lp = h[2 * n_tot :].view(torch.float32)
+        for i in live:
+            n, o = n_text[i], off[i]
+            b0 = base[i] + P0 - 1  # the row that scores the first text token
+            result[i] = Alignment(tokens=list(seqs[i][P0:]), first_frame=h[o : o + n].tolist(),
+                                  last_frame=h[n_tot + o : n_tot + o + n].tolist(),
+                                  logprobs=h_lp[b0 : b0 + n].tolist(), n_keys=n_keys[i],
+                                  cost=costs[i].cpu() if i in costs else None)
+        return result
+
+    def words_of(self, al: Alignment, *, duration: Optional[float] = None) -> List[Dict]:
+        """The Deepgram ``words`` list of one aligned utterance, on the utterance's own clock."""
+        tb = self.tok.token_bytes()
+        return group_words(al, lambda t: tb[t] if 0 <= t < len(tb) else b"", duration=duration)
 
     def _prompt_logits(self, slots: List[int], prompts: List[List[int]]) -> torch.Tensor:
         """Prefill every session's prompt (ragged rows, <= 64 per step; a session's rows stay in

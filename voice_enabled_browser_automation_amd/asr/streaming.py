@@ -43,9 +43,14 @@ from typing import Any, Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from .words import confidence as _confidence
+from .words import shift_words
+
 
 def results_event(text: str, *, is_final: bool, start: float, duration: float, model: str,
-                  confidence: float = 0.0) -> Dict:
+                  confidence: float = 0.0, words: Optional[List[Dict]] = None) -> Dict:
+    """``words``: the alternative's Deepgram word list ({"word", "punctuated_word", "start", "end",
+    "confidence"}, stream-clock seconds); None: the empty list."""
     return {
         "type": "Results",
         "channel_index": [0, 1],
@@ -53,17 +58,22 @@ def results_event(text: str, *, is_final: bool, start: float, duration: float, m
         "start": round(start, 3),
         "is_final": is_final,
         "speech_final": is_final,
-        "channel": {"alternatives": [{"transcript": text, "confidence": confidence, "words": []}]},
+        "channel": {"alternatives": [{"transcript": text, "confidence": confidence,
+                                      "words": list(words) if words else []}]},
         "metadata": {"model_info": {"name": model}},
     }
 
 
 @dataclass
 class Hypothesis:
-    """One recognition pass: the full transcript's token ids (forced prefix included) and text."""
+    """One recognition pass: the full transcript's token ids (forced prefix included) and text;
+    from a pass that was asked for them, the words (asr/words.py, seconds from the utterance's
+    start) and the transcript's confidence."""
 
     tokens: List[int] = field(default_factory=list)
     text: str = ""
+    words: List[Dict] = field(default_factory=list)
+    confidence: float = 0.0
 
 
 class TextRecognizer:
@@ -81,14 +91,15 @@ def _as_recognizer(r: Any):
     return r if hasattr(r, "recognize") else TextRecognizer(r)
 
 
-def recognize_async(rec: Any, pcm: np.ndarray, prefix: Sequence[int] = ()) -> Future:
+def recognize_async(rec: Any, pcm: np.ndarray, prefix: Sequence[int] = (), **kw) -> Future:
     """A recognition pass that runs in the background when the recognizer can (AsrBatcher: queued
-    for the next GPU batch), else synchronously into an already completed Future."""
+    for the next GPU batch), else synchronously into an already completed Future.  ``kw``: passed
+    on (``words=True``: a final pass of a session that wants word timestamps)."""
     if hasattr(rec, "recognize_async"):
-        return rec.recognize_async(pcm, prefix)
+        return rec.recognize_async(pcm, prefix, **kw)
     fut: Future = Future()
     try:
-        fut.set_result(rec.recognize(pcm, prefix))
+        fut.set_result(rec.recognize(pcm, prefix, **kw))
     except BaseException as e:  # noqa: BLE001
         fut.set_exception(e)
     return fut
@@ -107,8 +118,13 @@ class StreamingAsrSession:
                  partial_every_s: float = 1.0, endpoint_silence_s: Optional[float] = None,
                  energy_threshold: Optional[float] = None, max_window_s: float = 30.0, min_speech_s: float = 0.2,
                  local_agreement: bool = True, spec_silence_s: Optional[float] = None,
-                 noise_mult: Optional[float] = None):
+                 noise_mult: Optional[float] = None, words: Optional[bool] = None):
         from ..utils.env import knob
+
+        # word timestamps + confidences on final results (VWA_ASR_WORDS): the final pass and the
+        # speculative final pass -- whose hypothesis becomes the final -- are asked for them
+        # (recognize(..., words=True)); partials never are
+        self.words = bool(knob("VWA_ASR_WORDS")) if words is None else bool(words)
 
         self.rec = _as_recognizer(recognizer)
         self.rate = rate
@@ -165,9 +181,10 @@ class StreamingAsrSession:
         self._pcm[self._n : self._n + len(fr)] = fr
         self._n += len(fr)
 
-    def _run(self) -> Hypothesis:
+    def _run(self, final: bool = False) -> Hypothesis:
         t0 = time.perf_counter()
-        hyp = self.rec.recognize(self.buf, self.committed if self.local_agreement else ())
+        kw = {"words": True} if final and self.words else {}
+        hyp = self.rec.recognize(self.buf, self.committed if self.local_agreement else (), **kw)
         self.stats["asr_ms"] += (time.perf_counter() - t0) * 1e3
         self.stats["passes"] += 1
         return hyp
@@ -210,7 +227,8 @@ class StreamingAsrSession:
         """The final pass, started during the trailing silence (see module docstring)."""
         self.stats["spec_started"] += 1
         self._spec_t0 = time.perf_counter()
-        fut = recognize_async(self.rec, self.buf.copy(), self.committed if self.local_agreement else ())
+        fut = recognize_async(self.rec, self.buf.copy(), self.committed if self.local_agreement else (),
+                              **({"words": True} if self.words else {}))
         self._spec = fut
         if self.on_speculative is not None:
             fut.add_done_callback(self._spec_ready)
@@ -237,9 +255,13 @@ class StreamingAsrSession:
                 except Exception:  # noqa: BLE001  (a failed background pass: run the final now)
                     self._drop_spec()
             if hyp is None:
-                hyp = self._run()
+                hyp = self._run(final=True)
+            kw = {}
+            if self.words:
+                kw = dict(confidence=getattr(hyp, "confidence", 0.0),
+                          words=shift_words(getattr(hyp, "words", None) or [], self.t_offset))
             out.append(results_event(hyp.text, is_final=True, start=self.t_offset, duration=len(self.buf) / self.rate,
-                                     model=self.model_name))
+                                     model=self.model_name, **kw))
             self.stats["finals"] += 1
         self._reset_utterance()
         return out
@@ -324,18 +346,37 @@ class StreamingAsrSession:
 
 
 # ---------------------------------------------------------------------------------- recognizers
+def _words_knob(words: Optional[bool]) -> bool:
+    from ..utils.env import knob
+
+    return bool(knob("VWA_ASR_WORDS")) if words is None else bool(words)
+
+
+def _hypothesis(eng, full: List[int], n_samples: int, al=None) -> Hypothesis:
+    """The pass's hypothesis; with its alignment (a words pass) also the words, on the utterance's
+    own clock, and the transcript confidence (exp of the mean log-probability of its text tokens)."""
+    text = eng.tok.decode(full).strip()
+    if al is None:
+        return Hypothesis(full, text)
+    return Hypothesis(full, text, eng.words_of(al, duration=n_samples / 16000.0), _confidence(al.logprobs))
+
+
 class EngineRecognizer:
     """Serial recognizer on an AsrEngine (one pass at a time, caller's thread)."""
 
-    def __init__(self, asr_engine, *, max_tokens: int = 96):
+    def __init__(self, asr_engine, *, max_tokens: int = 96, words: Optional[bool] = None):
+        """words: serve passes that ask for word timestamps (None: the VWA_ASR_WORDS knob); off,
+        such a pass gets the plain hypothesis."""
         self.eng = asr_engine
         self.max_tokens = max_tokens
+        self.words = _words_knob(words)
 
-    def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = ()) -> Hypothesis:
+    def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False) -> Hypothesis:
         prefix = list(prefix)[: self.eng.max_prefix()]  # the prefix the decoder actually forces
-        toks = self.eng.decode_many([self.eng.pcm_to_audio(pcm)], [prefix], max_tokens=self.max_tokens)[0]
-        full = prefix + toks
-        return Hypothesis(full, self.eng.tok.decode(full).strip())
+        words = bool(words) and self.words
+        toks = self.eng.decode_many([self.eng.pcm_to_audio(pcm)], [prefix], max_tokens=self.max_tokens,
+                                    **({"words": True} if words else {}))[0]
+        return _hypothesis(self.eng, prefix + toks, len(pcm), self.eng.last_alignments[0] if words else None)
 
 
 class AsrBatcher:
@@ -347,13 +388,16 @@ class AsrBatcher:
     on the GPU the next one accumulates, so under load each GPU pass serves many sessions."""
 
     def __init__(self, asr_engine, *, max_tokens: int = 96, max_batch: Optional[int] = None,
-                 tokens_per_s: Optional[float] = None):
+                 tokens_per_s: Optional[float] = None, words: Optional[bool] = None):
         """tokens_per_s: fixed-work mode for benchmarks on random-init weights (which emit EOT at
         random): every pass decodes exactly round(audio seconds x tokens_per_s) transcript tokens
         in all (committed prefix included), as bench.py's ``exact_tokens``."""
         self.eng = asr_engine
         self.max_tokens = max_tokens
         self.tokens_per_s = tokens_per_s
+        # serve passes that ask for word timestamps (None: the VWA_ASR_WORDS knob): a batch with
+        # such a pass runs decode_many(words=True)
+        self.words = _words_knob(words)
         self.max_batch = max_batch or len(asr_engine.free_slots)
         self._q: List[tuple] = []
         self._cv = threading.Condition()
@@ -373,17 +417,18 @@ class AsrBatcher:
         self._thread = threading.Thread(target=self._loop, name="asr-batcher", daemon=True)
         self._thread.start()
 
-    def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = ()) -> Hypothesis:
-        return self.recognize_async(pcm, prefix).result()
+    def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False) -> Hypothesis:
+        return self.recognize_async(pcm, prefix, words=words).result()
 
-    def recognize_async(self, pcm: np.ndarray, prefix: Sequence[int] = ()) -> Future:
+    def recognize_async(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False) -> Future:
         """Queue a pass for the next GPU batch; the Future resolves to its Hypothesis."""
         fut: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("ASR batcher stopped")
             # (cut to what the decoder forces: the hypothesis is built on the prefix it really used)
-            self._q.append((np.array(pcm, dtype=np.int16, copy=True), list(prefix)[: self.eng.max_prefix()], fut))
+            self._q.append((np.array(pcm, dtype=np.int16, copy=True), list(prefix)[: self.eng.max_prefix()], fut,
+                            bool(words) and self.words))
             self._cv.notify()
         return fut
 
@@ -411,17 +456,20 @@ class AsrBatcher:
             if self.busy is not None:
                 self.busy.enter()
             try:
-                audios = [self.eng.pcm_to_audio(p) for p, _, _ in batch]
+                audios = [self.eng.pcm_to_audio(p) for p, _, _, _ in batch]
                 kw = dict(max_tokens=self.max_tokens)
                 if self.tokens_per_s:
                     kw = dict(exact_tokens=max(1, min(self.max_tokens, max(
-                        int(round(len(p) / 16000 * self.tokens_per_s)) - len(pre) for p, pre, _ in batch))))
-                toks = self.eng.decode_many(audios, [pre for _, pre, _ in batch], **kw)
-                for (_, pre, fut), t in zip(batch, toks):
-                    full = pre + t
-                    fut.set_result(Hypothesis(full, self.eng.tok.decode(full).strip()))
+                        int(round(len(p) / 16000 * self.tokens_per_s)) - len(pre) for p, pre, _, _ in batch))))
+                want = any(w for _, _, _, w in batch)
+                if want:
+                    kw["words"] = True
+                toks = self.eng.decode_many(audios, [pre for _, pre, _, _ in batch], **kw)
+                als = self.eng.last_alignments if want else [None] * len(batch)
+                for (p, pre, fut, w), t, al in zip(batch, toks, als):
+                    fut.set_result(_hypothesis(self.eng, pre + t, len(p), al if w else None))
             except BaseException as e:  # noqa: BLE001  (fail this batch's passes, keep serving)
-                for _, _, fut in batch:
+                for _, _, fut, _ in batch:
                     if not fut.done():
                         fut.set_exception(e)
             finally:

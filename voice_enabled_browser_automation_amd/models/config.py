@@ -6,7 +6,7 @@ north star (BASELINE.json) names these on-node replacements.
 from __future__ import annotations
 
 from dataclasses import dataclass, field, replace
-from typing import Optional
+from typing import Optional, Tuple
 
 
 @dataclass(frozen=True)
@@ -72,10 +72,20 @@ class WhisperConfig:
     lang_en: int = 50259
     transcribe: int = 50359
     no_timestamps: int = 50363
+    # (decoder layer, head) pairs whose cross-attention tracks the audio (word timestamps); None:
+    # every head of the upper half of the decoder layers.  A checkpoint's generation_config.json
+    # fills it (models/whisper.py); no per-model list is kept here.
+    alignment_heads: Optional[Tuple[Tuple[int, int], ...]] = None
 
     @property
     def head_dim(self) -> int:
         return self.d_model // self.n_heads
+
+    def align_heads(self) -> Tuple[Tuple[int, int], ...]:
+        """The alignment heads in (layer, head) order, the default filled in."""
+        if self.alignment_heads is not None:
+            return tuple(sorted((int(l), int(h)) for l, h in self.alignment_heads))
+        return tuple((l, h) for l in range(self.n_dec_layers // 2, self.n_dec_layers) for h in range(self.n_heads))
 
     @property
     def ffn(self) -> int:

@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import math
 import weakref
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import List, Optional, Sequence
 
 import torch
@@ -188,6 +188,10 @@ class DecLayer:
 class WhisperModel:
     def __init__(self, cfg: WhisperConfig, *, device="cpu", dtype=torch.bfloat16, seed: int = 0,
                  weights=None, tile_decoder: Optional[bool] = None):
+        gen_cfg = getattr(weights, "generation_config", lambda: None)() if weights is not None else None
+        if cfg.alignment_heads is None and gen_cfg and gen_cfg.get("alignment_heads"):
+            # the checkpoint's own word-timestamp heads ([[layer, head], ...])
+            cfg = replace(cfg, alignment_heads=tuple((int(l), int(h)) for l, h in gen_cfg["alignment_heads"]))
         self.cfg = cfg
         self.device = torch.device(device)
         self.dtype = dtype
@@ -665,4 +669,65 @@ class WhisperModel:
             f = ops.linear(x, w, b, act="gelu", out=bufs.f[:M], eps=eps, ln_c=c)
             ops.linear(f, L.fc2, L.fc2_b, out=x, residual=x)
         w, b, c = self.f_lm  # decoder layer_norm folded into the tied LM head
+        return ops.linear(x, w, b, out=bufs.logits[:M], eps=eps, ln_c=c)
+
+    # ------------------------------------------------------------------ word alignment
+    def align_layers(self):
+        """[(decoder layer, int32 device tensor of its alignment heads, first row of the layer's
+        heads in a probabilities buffer)], in layer order, and the total head count (built once)."""
+        if getattr(self, "_align_layers", None) is None:
+            by_layer: dict = {}
+            for l, h in self.cfg.align_heads():
+                if not (0 <= l < len(self.dec) and 0 <= h < self.H):
+                    raise ValueError(f"alignment head ({l}, {h}) outside {len(self.dec)} layers x {self.H} heads")
+                by_layer.setdefault(l, []).append(h)
+            out, off = [], 0
+            for l in sorted(by_layer):
+                out.append((l, torch.tensor(by_layer[l], dtype=torch.int32, device=self.device), off))
+                off += len(by_layer[l])
+            self._align_layers = (out, off)
+        return self._align_layers
+
+    def align_step(self, bufs, M: int, segments) -> torch.Tensor:
+        """A teacher-forced decoder step that also records the alignment heads' cross-attention
+        probabilities: decode_step's per-kernel loop (never the chained or persistent launches, not
+        graph-captured) with, after each alignment layer's cross-query projection, one attn_probs
+        call per segment.  ``segments``: (first row, rows, session slot, probs, first token row,
+        n_keys) -- rows [first row, first row + rows) of this step belong to that session and are
+        its tokens [first token row, ...); probs is its f32 [heads, tokens, n_audio_ctx] buffer in
+        align_layers() head order.  Returns f32 logits [M, vocab]."""
+        cfg = self.cfg
+        x = bufs.hidden[:M]
+        eps = cfg.ln_eps
+        scale = self.hd ** -0.5
+        heads_of = {l: (h, off) for l, h, off in self.align_layers()[0]}
+        ops.embedding(bufs.tokens, self.tok_emb, pos_table=self.pos_emb, positions=bufs.positions, out=x, rows=M)
+        for li, L in enumerate(self.dec):
+            w, b, c = L.f_qkv
+            q = ops.qkv_rope_write(x, w, b, fuse_rms=False, eps=eps, n_q_heads=self.H, n_kv_heads=self.H,
+                                   head_dim=self.hd, rope=None, positions=bufs.positions, slots=bufs.slots,
+                                   q_out=bufs.q, k_cache=bufs.k_cache[li], v_cache=bufs.v_cache[li], ln_c=c)
+            att = ops.decode_attention(q, ops.KVLayout.paged(bufs.k_cache[li], bufs.v_cache[li], bufs.block_table),
+                                       bufs.ctx_lens, bufs.seq_ids, n_q_heads=self.H, n_kv_heads=self.H,
+                                       head_dim=self.hd, scale=scale, max_ctx=bufs.max_ctx,
+                                       out=bufs.att[:M], part_o=bufs.part_o, part_ml=bufs.part_ml,
+                                       counters=bufs.attn_cnt)
+            ops.linear(att, L.o, L.o_b, out=x, residual=x)
+            w, b, c = L.f_xq
+            xq = ops.linear(x, w, b, out=bufs.q[:M], eps=eps, ln_c=c)
+            ck, cv = bufs.cross[li]
+            if li in heads_of:
+                heads, off = heads_of[li]
+                for r0, n, slot, probs, t0, n_keys in segments:
+                    ops.attn_probs(bufs.q[r0 : r0 + n], ck[slot], heads, n_keys, scale,
+                                   probs[off : off + heads.numel(), t0 : t0 + n])
+            att = ops.decode_attention(xq, ops.KVLayout.contiguous(ck, cv, bufs.cross_table), bufs.cross_lens,
+                                       bufs.seq_ids, n_q_heads=self.H, n_kv_heads=self.H, head_dim=self.hd,
+                                       scale=scale, max_ctx=ck.shape[1], out=bufs.att[:M],
+                                       part_o=bufs.part_o, part_ml=bufs.part_ml, counters=bufs.attn_cnt)
+            ops.linear(att, L.xo, L.xo_b, out=x, residual=x)
+            w, b, c = L.f_fc1
+            f = ops.linear(x, w, b, act="gelu", out=bufs.f[:M], eps=eps, ln_c=c)
+            ops.linear(f, L.fc2, L.fc2_b, out=x, residual=x)
+        w, b, c = self.f_lm
         return ops.linear(x, w, b, out=bufs.logits[:M], eps=eps, ln_c=c)

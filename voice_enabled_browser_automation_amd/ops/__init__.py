@@ -1146,6 +1146,115 @@ def conv1d_gelu(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], *, 
     return out
 
 
+# ----------------------------------------------------------------------------- word alignment
+_ALIGN = None
+_ALIGN_ERR: Optional[BaseException] = None
+DTW_MAX_ROWS = 448       # csrc/align/align.h kDtwMaxRows: one lane per token row
+DTW_LDS_TRACE = 48 * 1024  # cells whose step trace the DTW kernel keeps in LDS
+
+
+def align_ext():
+    """Load the word-alignment kernel library ``_vwa_align.so`` (once). Raises if unavailable."""
+    global _ALIGN, _ALIGN_ERR
+    if _ALIGN is not None:
+        return _ALIGN
+    if _ALIGN_ERR is not None:
+        raise RuntimeError(f"native gfx950 alignment library unavailable: {_ALIGN_ERR}") from _ALIGN_ERR
+    try:
+        from . import _vwa_align as m  # type: ignore
+
+        _ALIGN = m
+        return m
+    except BaseException as e:  # noqa: BLE001
+        _ALIGN_ERR = e
+        raise RuntimeError(
+            "native gfx950 alignment library _vwa_align.so failed to load; build it with "
+            "`python -m voice_enabled_browser_automation_amd.ops.build`"
+        ) from e
+
+
+def attn_probs(q: torch.Tensor, k: torch.Tensor, heads, n_keys: int, scale: float, out: torch.Tensor) -> torch.Tensor:
+    """Attention probabilities of selected heads: ``out[s, t, :n_keys] = softmax_j(scale * q[t, heads[s]] .
+    k[j, heads[s]])``.  q bf16 [T, H*64], k bf16 [S_max, H, 64] (one session's cross K), out f32
+    [n_sel, T, S_max]; columns >= n_keys are not written.  ``heads``: an int32 tensor on q's
+    device, or a list of ints (checked against [0, H) here)."""
+    H = k.shape[1]
+    if not isinstance(heads, torch.Tensor):
+        heads = [int(h) for h in heads]
+        if not heads or min(heads) < 0 or max(heads) >= H:
+            raise ValueError(f"attn_probs: heads {heads} not all in [0, {H})")
+        heads = torch.tensor(heads, dtype=torch.int32, device=q.device)
+    if not _gpu(q):
+        return ref.attn_probs(q, k, heads, n_keys, scale, out)
+    align_ext().attn_probs(q, k, heads, n_keys, scale, out)
+    return out
+
+
+def align_cost(probs: torch.Tensor, n_tokens: int, n_keys: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Token x frame alignment cost from f32 probabilities [Hs, T, S_max]: per head and frame the
+    z-score over the first n_tokens rows, median of 7 along the frames (reflect padding; none for
+    n_keys <= 3), mean over heads, negated.  Writes out[:n_tokens, :n_keys] of f32 [T, S_max]."""
+    if out is None:
+        out = torch.empty(probs.shape[1], probs.shape[2], dtype=torch.float32, device=probs.device)
+    if not _gpu(probs):
+        return ref.align_cost(probs, n_tokens, n_keys, out)
+    align_ext().align_cost(probs, n_tokens, n_keys, out)
+    return out
+
+
+def dtw_path(cost: torch.Tensor, n_tokens: int, n_keys: int, first_frame: Optional[torch.Tensor] = None,
+             last_frame: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """Dynamic time warping over cost[:n_tokens, :n_keys] (f32 [T, S_max]) from (0, 0) to the last
+    cell; returns int32 (first_frame, last_frame): the smallest / largest frame of the path in each
+    token row.  On the GPU one launch (backtrack included); matrices over DTW_LDS_TRACE cells take a
+    uint8 ``workspace`` of n_tokens * n_keys bytes (allocated here when not given)."""
+    if not (1 <= n_tokens <= min(cost.shape[0], DTW_MAX_ROWS) and 1 <= n_keys <= cost.shape[1]):
+        raise ValueError(f"dtw_path: {n_tokens} x {n_keys} outside cost {tuple(cost.shape)} / {DTW_MAX_ROWS} token rows")
+    if first_frame is None:
+        first_frame = torch.empty(n_tokens, dtype=torch.int32, device=cost.device)
+    if last_frame is None:
+        last_frame = torch.empty(n_tokens, dtype=torch.int32, device=cost.device)
+    if not _gpu(cost):
+        return ref.dtw_path(cost, n_tokens, n_keys, first_frame, last_frame)
+    if workspace is None and n_tokens * n_keys > DTW_LDS_TRACE:
+        workspace = torch.empty(n_tokens * n_keys, dtype=torch.uint8, device=cost.device)
+    align_ext().dtw_path(cost, n_tokens, n_keys, first_frame, last_frame, workspace)
+    return first_frame, last_frame
+
+
+def mask_allows(mask, row: int, token: int) -> bool:
+    """Bit ``token`` of row ``row`` (row 0 of a one-row mask) of a packed allow-mask on the host."""
+    m = mask.reshape(-1, mask.shape[-1])
+    return bool((int(m[row if m.shape[0] > 1 else 0, token // 32]) >> (token % 32)) & 1)
+
+
+def token_logprob(logits: torch.Tensor, targets, mask: Optional[torch.Tensor], vocab: int,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[n] = logits[n, t_n] - logsumexp`` over the ids below ``vocab`` that the packed
+    allow-mask (int32 [N or 1, words], bit set = allowed; None: all) admits.  logits f32
+    [N, >= vocab].  ``targets``: int32 tensor [N], or a list of ints -- then a target outside
+    [0, vocab) raises here, and so does one a host-resident mask forbids (the device clamps the
+    former; the latter gives -inf)."""
+    N = logits.shape[0]
+    if not isinstance(targets, torch.Tensor):
+        targets = [int(t) for t in targets]
+        if len(targets) != N or min(targets) < 0 or max(targets) >= vocab:
+            raise ValueError(f"token_logprob: {N} targets in [0, {vocab}) expected")
+        if mask is not None and not mask.is_cuda:
+            for n, t in enumerate(targets):
+                if not mask_allows(mask, n, t):
+                    raise ValueError(f"token_logprob: target {t} of row {n} is masked out")
+        targets = torch.tensor(targets, dtype=torch.int32, device=logits.device)
+    if mask is not None and mask.dim() == 1:
+        mask = mask[None]
+    if out is None:
+        out = torch.empty(N, dtype=torch.float32, device=logits.device)
+    if not _gpu(logits):
+        return ref.token_logprob(logits, targets, mask, vocab, out)
+    align_ext().token_logprob(logits, targets, mask, vocab, out)
+    return out
+
+
 def env_flag(name: str) -> bool:
     """A boolean knob (utils/env.py Settings: declared type and default)."""
     return bool(knob(name))

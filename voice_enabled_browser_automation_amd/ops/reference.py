@@ -334,3 +334,81 @@ def mel_filterbank(sr: int = 16000, n_fft: int = 400, n_mels: int = 80) -> torch
     enorm = 2.0 / (hz[2 : n_mels + 2] - hz[:n_mels])
     weights = weights * enorm[:, None]
     return weights.float()
+
+
+# ----------------------------------------------------------------------------- word alignment
+# (csrc/align: the same contracts in f32 torch / numpy)
+def attn_probs(q, k, heads, n_keys, scale, out):
+    """out[s, t, :n_keys] = softmax_j(scale * q[t, head s] . k[j, head s]); other columns untouched."""
+    S, H, hd = k.shape
+    qf = q.float().view(q.shape[0], H, hd)
+    for s, h in enumerate(int(v) for v in heads.tolist()):
+        sc = (qf[:, h] @ k[:n_keys, h].float().t()) * scale
+        out[s, :, :n_keys] = torch.softmax(sc, dim=-1)
+    return out
+
+
+def align_cost(probs, n_tokens, n_keys, out):
+    """out[:n_tokens, :n_keys] = -mean_h median7_j(z-score over the token rows); reflect padding,
+    no filter when n_keys <= 3."""
+    p = probs[:, :n_tokens, :n_keys].float()
+    mu = p.mean(dim=1, keepdim=True)
+    var = (p - mu).pow(2).mean(dim=1, keepdim=True)
+    z = (p - mu) / torch.sqrt(var + 1e-12)
+    if n_keys > 3:
+        z = F.pad(z, (3, 3), mode="reflect").unfold(-1, 7, 1).sort(dim=-1).values[..., 3]
+    out[:n_tokens, :n_keys] = -z.mean(dim=0)
+    return out
+
+
+def dtw_path(cost, n_tokens, n_keys, first_frame, last_frame):
+    """f32 DTW (anti-diagonal order, as the kernel) with the tie rule diagonal < vertical <
+    horizontal-by-default, and the backtrack from (n_tokens-1, n_keys-1)."""
+    import numpy as np
+
+    c = cost[:n_tokens, :n_keys].detach().cpu().numpy().astype(np.float32)
+    T, N = c.shape
+    inf = np.float32(np.inf)
+    D = np.full((T + 1, N + 1), inf, dtype=np.float32)  # D[i+1][j+1]: cell (i, j)
+    step = np.full((T, N), 2, dtype=np.int8)
+    for d in range(T + N - 1):
+        i = np.arange(max(0, d - N + 1), min(T, d + 1))
+        j = d - i
+        c0, c1, c2 = D[i, j], D[i, j + 1], D[i + 1, j]
+        diag = (c0 < c1) & (c0 < c2)
+        vert = ~diag & (c1 < c0) & (c1 < c2)
+        best = np.where(diag, c0, np.where(vert, c1, c2))
+        if d == 0:
+            best = np.zeros(1, dtype=np.float32)
+        D[i + 1, j + 1] = c[i, j] + best
+        step[i, j] = np.where(diag, 0, np.where(vert, 1, 2))
+    first = np.zeros(T, dtype=np.int64)
+    last = np.zeros(T, dtype=np.int64)
+    r, j = T - 1, N - 1
+    last[r] = j
+    while r > 0 or j > 0:
+        s = 2 if r == 0 else 1 if j == 0 else int(step[r, j])
+        if s != 2:
+            first[r] = j
+            r -= 1
+            if s == 0:
+                j -= 1
+            last[r] = j
+        else:
+            j -= 1
+    first_frame[:T] = torch.from_numpy(first).to(first_frame.dtype)
+    last_frame[:T] = torch.from_numpy(last).to(last_frame.dtype)
+    return first_frame, last_frame
+
+
+def token_logprob(logits, targets, mask, vocab, out):
+    """out[n] = logits[n, t_n] - logsumexp over allowed ids < vocab (mask: packed bits [N or 1, words])."""
+    N = logits.shape[0]
+    x = logits[:, :vocab].float()
+    if mask is not None:
+        ids = torch.arange(vocab)
+        bits = (mask.reshape(-1, mask.shape[-1])[:, ids // 32] >> (ids % 32)) & 1
+        x = x.masked_fill(bits.expand(N, -1) == 0, float("-inf"))
+    t = targets[:N].long().clamp(0, vocab - 1)
+    out[:N] = (x.gather(1, t[:, None])[:, 0] - torch.logsumexp(x, dim=-1)).clamp_max(0.0)
+    return out

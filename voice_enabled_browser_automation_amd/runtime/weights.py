@@ -38,6 +38,7 @@ class LazySafetensors:
             files = [path]
         if not files:
             raise FileNotFoundError(f"no .safetensors files under {path}")
+        self.dir = path if os.path.isdir(path) else os.path.dirname(os.path.abspath(path))
         self._handles = [safe_open(f, framework="pt", device="cpu") for f in files]
         self._where: Dict[str, int] = {}
         for i, h in enumerate(self._handles):
@@ -55,6 +56,14 @@ class LazySafetensors:
 
     def __len__(self) -> int:
         return len(self._where)
+
+    def generation_config(self) -> Optional[dict]:
+        """The ``generation_config.json`` beside the checkpoint (Whisper: ``alignment_heads``), or None."""
+        p = os.path.join(self.dir, "generation_config.json")
+        if not os.path.exists(p):
+            return None
+        with open(p) as fh:
+            return json.load(fh)
 
 
 def load_llm(name: str, *, device, tp=None, seed: int = 0, weights_path: Optional[str] = None,

@@ -113,6 +113,7 @@ class Settings(BaseModel):
     VWA_VAD_NOISE_MULT: float = Field(3.0, description="speech frame RMS >= this x the tracked noise floor")
     VWA_PARTIAL_EVERY_S: float = Field(1.0, description="interim result period during speech")
     VWA_ASR_TOKENS_PER_S: float = Field(0.0, description="fixed-work transcripts (benchmarks on random weights; 0: off)")
+    VWA_ASR_WORDS: bool = Field(False, description="final transcript events carry per-word start / end / confidence and the transcript confidence (an alignment pass after each final recognition pass: csrc/align)")
     VWA_CONTEXT_MAX_BYTES: int = Field(2048, description="per-session context cap sent to the brain")
     # ---- engine
     VWA_HIPGRAPH: bool = Field(True, description="replay decode steps from captured hipGraphs")
