@@ -3,6 +3,7 @@ launches (models/whisper.py, skinny_stream.hip chain_kernel SEQ 1/2), fixed 40-t
 bench's synthetic 10 s utterance.  One JSON line per mode.
 python tools/asr_timing.py [--asr whisper-large-v3] [--reps 10]
 python tools/asr_timing.py --words [--asr whisper-large-v3]   # the final pass without / with word timestamps
+python tools/asr_timing.py --language auto [--asr whisper-large-v3]   # the pass with a fixed / a detected language
 
 decode_us_per_token = host time from the encoder's launch to the last token / tokens (includes the
 encoder and cross K/V projections still running after their launch); decode_gpu_us_per_token = the
@@ -36,6 +37,9 @@ def main():
                          "one-launch decoder (VWA_ASR_PERSIST, whisper-large)")
     ap.add_argument("--words", action="store_true",
                     help="time the final pass without and with word timestamps (the alignment pass after the decode)")
+    ap.add_argument("--language", default=None,
+                    help="time the same pass with the default fixed language and with this one (auto: detected from "
+                         "the start-of-transcript logits, one more one-row decoder step and the probe)")
     ap.add_argument("--small-max-m", type=int, default=None,
                     help="A/B: rows up to which small weights take the one-tile kernel (16: the tiled GEMM above 16)")
     a = ap.parse_args()
@@ -84,6 +88,29 @@ def main():
                                   total_ms_q3=round(q[2], 3), align_ms=round(statistics.median(al), 3),
                                   align_heads=m.align_layers()[1])), flush=True)
         print(json.dumps(dict(tool="asr_timing", asr=a.asr, same_tokens=toks[False] == toks[True])), flush=True)
+        return
+    if a.language:  # the pass with the fixed default language and with --language (decode_many(languages=))
+        eng = AsrEngine(m, load_tokenizer("whisper"), max_sessions=2)
+        audio = eng.pcm_to_audio(synth_speech(10.0, seed=100))
+        for lang in (None, a.language, None, a.language):  # interleaved, reps each
+            kw = {} if lang is None else {"languages": [lang]}
+            for _ in range(2):
+                eng.decode_many([audio], exact_tokens=a.tokens, **kw)
+            tot, dgpu = [], []
+            for _ in range(a.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                eng.decode_many([audio], exact_tokens=a.tokens, **kw)
+                tot.append((time.perf_counter() - t0) * 1e3)
+                dgpu.append(eng.last_stats.get("decode_gpu_ms") or 0.0)
+            q = statistics.quantiles(tot, n=4) if len(tot) >= 4 else [min(tot), statistics.median(tot), max(tot)]
+            sot = eng.last_sot[0]
+            print(json.dumps(dict(tool="asr_timing", asr=a.asr, language=lang or eng.language, tokens=a.tokens,
+                                  reps=a.reps, total_ms=round(statistics.median(tot), 3),
+                                  total_ms_min=round(min(tot), 3), total_ms_max=round(max(tot), 3),
+                                  total_ms_q1=round(q[0], 3), total_ms_q3=round(q[2], 3),
+                                  decode_gpu_ms=round(statistics.median(dgpu), 3), used_language=sot["language"],
+                                  no_speech_prob=sot["no_speech_prob"])), flush=True)
         return
     audio = None
     texts = {}

@@ -17,6 +17,7 @@ import torch
 
 from .. import ops
 from ..models.whisper import WhisperModel
+from ..tokenizer.languages import language_code, language_index, language_token
 from .words import Alignment, group_words
 
 BUCKETS = (1, 2, 4, 8, 16, 32, 64)
@@ -116,10 +117,13 @@ class WhisperRunner:
         self.graphs[M] = (g, out)
         return self.graphs[M]
 
-    def step(self, rows: Sequence[Tuple[int, int, int]], fwd=None) -> torch.Tensor:
+    def step(self, rows: Sequence[Tuple[int, int, int]], fwd=None, pre=None) -> torch.Tensor:
         """rows: (session slot, token, position). Returns f32 logits [len(rows), vocab_padded].
         ``fwd``: the forward to run on the staged rows instead of the (graph-replayed) decode step --
-        ``fwd(M) -> logits`` (the word-alignment pass, never captured)."""
+        ``fwd(M) -> logits`` (the word-alignment pass, never captured).
+        ``pre``: called between the staging copy and the forward / graph replay -- stream-ordered
+        work that rewrites staged rows on the device (the SOT probe putting a detected language
+        token into ``b.tokens``: AsrEngine._prompt_auto)."""
         n = len(rows)
         M = next(bk for bk in BUCKETS if bk >= n)
         if self._copy_done is not None:
@@ -142,6 +146,8 @@ class WhisperRunner:
             if self._copy_done is None:
                 self._copy_done = torch.cuda.Event()
             self._copy_done.record()
+        if pre is not None:
+            pre()
         if fwd is not None:
             out = fwd(M)
         elif self.use_graphs:
@@ -155,7 +161,16 @@ class WhisperRunner:
 class AsrEngine:
     """Whisper transcription with fixed-work decoding options for benchmarking."""
 
-    def __init__(self, model: WhisperModel, tokenizer, *, max_sessions: int = 4, use_graphs: Optional[bool] = None):
+    def __init__(self, model: WhisperModel, tokenizer, *, max_sessions: int = 4, use_graphs: Optional[bool] = None,
+                 language: Optional[str] = None, task: Optional[str] = None,
+                 languages_allowed: Optional[Sequence[str]] = None, no_speech_threshold: Optional[float] = None):
+        """language: the default language code of a session, or "auto" (detect per pass);
+        task: "transcribe" | "translate"; languages_allowed: codes detection may report (None: all
+        the model has); no_speech_threshold: a session whose no-speech probability exceeds it is
+        reported as gated (0: the probability is not computed).  None: the VWA_ASR_LANGUAGE /
+        VWA_ASR_TASK / VWA_ASR_LANGUAGES / VWA_ASR_NO_SPEECH settings."""
+        from ..utils.env import knob
+
         self.model = model
         self.tok = tokenizer
         cfg = model.cfg
@@ -172,7 +187,26 @@ class AsrEngine:
         self.d_tok = torch.zeros(1, dtype=torch.int32, device=dev)
         self.part_val = torch.zeros(64, dtype=torch.float32, device=dev)
         self.part_idx = torch.zeros(64, dtype=torch.int32, device=dev)
-        self.prompt = [cfg.sot, cfg.lang_en, cfg.transcribe, cfg.no_timestamps]
+        self.language = str(knob("VWA_ASR_LANGUAGE") if language is None else language).strip().lower()
+        self.task = str(knob("VWA_ASR_TASK") if task is None else task).strip().lower()
+        if languages_allowed is None:
+            languages_allowed = knob("VWA_ASR_LANGUAGES") or None
+        if isinstance(languages_allowed, str):
+            languages_allowed = [c for c in (x.strip() for x in languages_allowed.split(",")) if c]
+        self.allow = (1 << cfg.n_langs) - 1  # bit i: detection may report language i
+        if languages_allowed:
+            self.allow = sum({1 << language_index(cfg, c) for c in languages_allowed})
+        self.no_speech_threshold = float(knob("VWA_ASR_NO_SPEECH") if no_speech_threshold is None
+                                         else no_speech_threshold)
+        # an "auto" session's language row until the probe patches it: the lowest allowed language
+        self._lang_placeholder = cfg.lang_en + (self.allow & -self.allow).bit_length() - 1
+        # the default session's SOT sequence (an "auto" default: the placeholder language)
+        self.prompt = [cfg.sot,
+                       self._lang_placeholder if self.language == "auto" else language_token(cfg, self.language),
+                       self._task_id(self.task), cfg.no_timestamps]
+        # decode_many: one entry per utterance of the last call -- language (code), language_confidence,
+        # no_speech_prob, gated; with keep_sot also "logits" (the SOT row, host) and "lang_probs"
+        self.last_sot: List[Dict] = []
         # device-resident single-session decode loop (graphs keyed by (slot, eot allowed))
         self.loop_out = torch.zeros(max(448, cfg.n_text_ctx), dtype=torch.int32, device=dev)
         self.loop_cnt = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -182,6 +216,14 @@ class AsrEngine:
         # decode_many(words=True): one entry per utterance of the last call (asr/words.py Alignment)
         self.last_alignments: List[Alignment] = []
         self.free_slots = list(range(max_sessions - 1, -1, -1))
+
+    keep_sot = False  # decode_many: always probe; keep host copies of the SOT logits and language probabilities
+
+    def _task_id(self, task: str) -> int:
+        cfg = self.model.cfg
+        if task not in ("transcribe", "translate"):
+            raise ValueError(f"unknown ASR task {task!r}: transcribe | translate")
+        return cfg.transcribe if task == "transcribe" else cfg.translate
 
     @staticmethod
     def _pack(bits: np.ndarray) -> np.ndarray:
@@ -326,7 +368,8 @@ class AsrEngine:
 
     def decode_many(self, audios: List[torch.Tensor], prefixes: Optional[Sequence[Sequence[int]]] = None, *,
                     max_tokens: int = 96, min_tokens: int = 0, exact_tokens: Optional[int] = None,
-                    words: bool = False) -> List[List[int]]:
+                    words: bool = False, languages: Optional[Sequence[Optional[str]]] = None,
+                    task: Optional[str] = None) -> List[List[int]]:
         """Token ids decoded for each utterance.  ``prefixes[i]``: text tokens forced after the
         SOT sequence (a streaming session's committed transcript -- asr/streaming.py local
         agreement): they are prefilled in the same ragged prompt step as the SOT tokens and only
@@ -336,7 +379,15 @@ class AsrEngine:
         ``words``: also align the transcript (prefix + decoded tokens) to the audio and score its
         tokens, before the session slots are released -- ``self.last_alignments[i]`` then holds
         utterance i's token ids, first / last 20 ms frame per token and token log-probabilities
-        (``_align``).  Off: nothing is allocated or launched for it."""
+        (``_align``).  Off: nothing is allocated or launched for it.
+
+        ``languages[i]``: utterance i's language code, "auto" (detected from the logits at the SOT
+        position, restricted to the engine's allowed languages) or None (the engine's default);
+        ``task``: "transcribe" | "translate" (None: the engine's).  ``self.last_sot[i]`` reports the
+        language used, and -- when a session is "auto", the no-speech gate is on or ``keep_sot`` is
+        set -- its confidence and the no-speech probability (``_probe``).  With every language fixed
+        and the gate off nothing is launched for it; a gated session is still decoded (skipping it
+        would take a host wait on every un-gated call)."""
         t0 = time.perf_counter()
         m = self.model
         B = len(audios)
@@ -346,7 +397,17 @@ class AsrEngine:
         assert len(prefixes) == B
         r = self.runner
         cap = r.bps * r.bs  # decoder positions per session
-        prompts = [self.prompt + p[: max(0, cap - len(self.prompt) - 1)] for p in prefixes]
+        cfg = m.cfg
+        langs = [self.language if l is None else str(l).strip().lower()
+                 for l in (languages if languages is not None else [None] * B)]
+        assert len(langs) == B
+        auto = [l == "auto" for l in langs]
+        task_id = self._task_id(self.task if task is None else str(task).strip().lower())
+        heads = [[cfg.sot, self._lang_placeholder if a else language_token(cfg, l), task_id, cfg.no_timestamps]
+                 for l, a in zip(langs, auto)]
+        prompts = [h + p[: max(0, cap - len(h) - 1)] for h, p in zip(heads, prefixes)]
+        probe = any(auto) or self.no_speech_threshold > 0.0 or self.keep_sot
+        sot = None
         slots = [self.free_slots.pop() for _ in range(B)]
         retry = False
         try:
@@ -361,7 +422,14 @@ class AsrEngine:
             if m.device.type == "cuda":
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
-            logits = self._prompt_logits(slots, prompts)
+            if not probe:
+                logits = self._prompt_logits(slots, prompts)
+            elif not any(auto):
+                # the SOT row's logits do not depend on the rows after it: the one prompt step serves
+                logits, sot_logits = self._prompt_logits(slots, prompts, first=True)
+                sot = self._probe(sot_logits)
+            else:
+                logits, sot = self._prompt_auto(slots, prompts, auto)
             outs: List[List[int]] = [[] for _ in range(B)]
             live = list(range(B))
             n_max = exact_tokens if exact_tokens is not None else max_tokens
@@ -397,6 +465,7 @@ class AsrEngine:
                                    tokens=sum(len(o) for o in outs), batch=B,
                                    prefix_tokens=sum(len(p) - len(self.prompt) for p in prompts))
             if not retry:
+                self.last_sot = self._read_sot(sot, langs, prompts)  # (fills in the detected language tokens)
                 if words:
                     self.last_alignments = self._align(slots, audios, prompts, outs, exact_tokens is not None,
                                                        min_tokens)
@@ -405,7 +474,7 @@ class AsrEngine:
         finally:
             self.free_slots.extend(slots)
         return self.decode_many(audios, prefixes, max_tokens=max_tokens, min_tokens=min_tokens,
-                                exact_tokens=exact_tokens, words=words)
+                                exact_tokens=exact_tokens, words=words, languages=languages, task=task)
 
     keep_costs = False  # _align: also keep each utterance's cost matrix (host copy) in its Alignment
 
@@ -506,33 +575,122 @@ class AsrEngine:
         tb = self.tok.token_bytes()
         return group_words(al, lambda t: tb[t] if 0 <= t < len(tb) else b"", duration=duration)
 
-    def _prompt_logits(self, slots: List[int], prompts: List[List[int]]) -> torch.Tensor:
+    def _prompt_logits(self, slots: List[int], prompts: List[List[int]], *, first: bool = False, start: int = 0,
+                       pre=None):
         """Prefill every session's prompt (ragged rows, <= 64 per step; a session's rows stay in
-        order) and return the logits of each session's LAST prompt row, in session order."""
+        order) and return the logits of each session's LAST prompt row, in session order.
+        ``first``: return (those, the logits of each session's position-0 row) -- the SOT row the
+        probe reads.  ``start``: the prompts' first ``start`` tokens are prefilled already.
+        ``pre(rows)``: run between a step's staging copy and its forward (WhisperRunner.step)."""
         R = max(BUCKETS)
         rows: List[Tuple[int, int, int]] = []
         want: List[int] = []   # row index (within the pending step) of a session's last prompt token
+        want0: List[int] = []  # ... of a session's position-0 row (first)
         got: List[torch.Tensor] = []
+        got0: List[torch.Tensor] = []
 
         def run():
-            nonlocal rows, want
+            nonlocal rows, want, want0
             if rows:
-                out = self.runner.step(rows)
+                out = self.runner.step(rows, pre=None if pre is None else (lambda r=rows: pre(r)))
                 if want:
                     # (clone: the logits live in the replayed graph's static output buffer)
                     got.append(out[torch.tensor(want, device=out.device)].clone())
-            rows, want = [], []
+                if want0:
+                    got0.append(out[torch.tensor(want0, device=out.device)].clone())
+            rows, want, want0 = [], [], []
 
         for slot, prompt in zip(slots, prompts):
-            if len(rows) + len(prompt) > R and len(prompt) <= R:
+            n = len(prompt) - start
+            if len(rows) + n > R and n <= R:
                 run()
-            for p, t in enumerate(prompt):
+            for p in range(start, len(prompt)):
                 if len(rows) == R:
                     run()
-                rows.append((slot, t, p))
+                rows.append((slot, prompt[p], p))
+                if first and p == 0:
+                    want0.append(len(rows) - 1)
             want.append(len(rows) - 1)
         run()
-        return torch.cat(got)
+        return (torch.cat(got), torch.cat(got0)) if first else torch.cat(got)
+
+    def _probe(self, sot_logits: torch.Tensor, tok_dst: Optional[torch.Tensor] = None,
+               dst_rows: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None):
+        """ops.sot_probe on the sessions' SOT-row logits [B, vocab_padded].  Every output lives in
+        one f32 buffer ``res`` = [B x n_langs probabilities | B language ids (int32 bits) | B
+        confidences | B no-speech probabilities]: one device-to-host copy reads it (_read_sot).
+        Returns (res, sot_logits)."""
+        cfg = self.model.cfg
+        B, n = sot_logits.shape[0], cfg.n_langs
+        if res is None:
+            res = torch.empty(B * (n + 3), dtype=torch.float32, device=sot_logits.device)
+        o = B * n
+        ops.sot_probe(sot_logits, cfg.vocab_size, cfg.lang_en, n, cfg.no_speech, self.allow,
+                      lang_probs=res[:o].view(B, n), lang_tok=res[o : o + B].view(torch.int32),
+                      lang_conf=res[o + B : o + 2 * B], no_speech=res[o + 2 * B :], tok_dst=tok_dst, dst_rows=dst_rows)
+        return res, sot_logits
+
+    def _prompt_auto(self, slots: List[int], prompts: List[List[int]], auto: List[bool]):
+        """The prompt with language detection, in two decoder steps and no host wait between them:
+        step 1 is every session's SOT row alone; step 2 the rest of every prompt from position 1,
+        the auto sessions with a placeholder language token.  Between step 2's staging copy and its
+        forward (or graph replay) the probe reads step 1's logits and writes each auto session's
+        detected language id over the placeholder in the staged token rows (``b.tokens``) -- so the
+        language row is embedded from the detected id, stream-ordered, on the device.  Fixed
+        sessions get no patch (dst_rows -1) and still get their probabilities."""
+        b = self.runner.b
+        dev = self.model.device
+        B = len(slots)
+        R = max(BUCKETS)
+        sot_rows = [(s, p[0], 0) for s, p in zip(slots, prompts)]
+        # (clone: the logits live in the replayed graph's static output buffer, which step 2 rewrites)
+        parts = [self.runner.step(sot_rows[a : a + R]).clone() for a in range(0, B, R)]
+        sot_logits = parts[0] if len(parts) == 1 else torch.cat(parts)
+        where = {s: i for i, s in enumerate(slots) if auto[i]}
+        state: Dict[str, torch.Tensor] = {}
+
+        def pre(rows):
+            dst = [-1] * B
+            for k, (slot, _tok, pos) in enumerate(rows):
+                if pos == 1 and slot in where:
+                    dst[where[slot]] = k
+            h = torch.tensor(dst, dtype=torch.int32)
+            if dev.type == "cuda":  # (pinned + non-blocking: the host does not wait for step 1)
+                h = h.pin_memory()
+            state["res"], _ = self._probe(sot_logits, b.tokens, h.to(dev, non_blocking=True), state.get("res"))
+
+        logits = self._prompt_logits(slots, prompts, start=1, pre=pre)
+        return logits, (state["res"], sot_logits)
+
+    def _read_sot(self, sot, langs: List[str], prompts: List[List[int]]) -> List[Dict]:
+        """last_sot of a call: the probe's outputs in ONE device-to-host copy (after the tokens were
+        read: the stream is already there).  An auto session's detected token replaces the
+        placeholder in its prompt (``_align`` teacher-forces the prompt the decoder really saw)."""
+        cfg = self.model.cfg
+        B = len(langs)
+        if sot is None:
+            return [dict(language=l, language_confidence=None, no_speech_prob=None, gated=False) for l in langs]
+        res, sot_logits = sot
+        n = cfg.n_langs
+        h = res.cpu()
+        probs = h[: B * n].view(B, n)
+        tok = h[B * n : B * n + B].view(torch.int32).tolist()
+        conf = h[B * n + B : B * n + 2 * B].tolist()
+        nsp = h[B * n + 2 * B :].tolist()
+        h_logits = sot_logits.cpu() if self.keep_sot else None
+        thr = self.no_speech_threshold
+        out = []
+        for i, l in enumerate(langs):
+            if l == "auto":
+                prompts[i][1] = tok[i]
+                d = dict(language=language_code(cfg, tok[i]), language_confidence=conf[i])
+            else:
+                d = dict(language=l, language_confidence=float(probs[i, language_index(cfg, l)]))
+            d.update(no_speech_prob=nsp[i], gated=thr > 0.0 and nsp[i] > thr)
+            if self.keep_sot:
+                d.update(logits=h_logits[i], lang_probs=probs[i].clone())
+            out.append(d)
+        return out
 
     def _chain_failed(self) -> bool:
         """Health check of the chained decoder launches (models/whisper.py): a grid barrier that

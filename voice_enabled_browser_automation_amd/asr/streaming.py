@@ -48,10 +48,14 @@ from .words import shift_words
 
 
 def results_event(text: str, *, is_final: bool, start: float, duration: float, model: str,
-                  confidence: float = 0.0, words: Optional[List[Dict]] = None) -> Dict:
+                  confidence: float = 0.0, words: Optional[List[Dict]] = None, language: Optional[str] = None,
+                  language_confidence: Optional[float] = None, no_speech_prob: Optional[float] = None) -> Dict:
     """``words``: the alternative's Deepgram word list ({"word", "punctuated_word", "start", "end",
-    "confidence"}, stream-clock seconds); None: the empty list."""
-    return {
+    "confidence"}, stream-clock seconds); None: the empty list.  ``language``: the detected (or
+    set) language code -- Deepgram's ``channel.detected_language`` / ``language_confidence`` and
+    the alternative's ``languages``.  ``no_speech_prob``: of a final the no-speech gate emptied
+    (``metadata.no_speech_prob``).  Without them the event is unchanged."""
+    ev = {
         "type": "Results",
         "channel_index": [0, 1],
         "duration": round(duration, 3),
@@ -62,18 +66,30 @@ def results_event(text: str, *, is_final: bool, start: float, duration: float, m
                                       "words": list(words) if words else []}]},
         "metadata": {"model_info": {"name": model}},
     }
+    if language is not None:
+        ev["channel"]["detected_language"] = language
+        ev["channel"]["language_confidence"] = 0.0 if language_confidence is None else language_confidence
+        ev["channel"]["alternatives"][0]["languages"] = [language]
+    if no_speech_prob is not None:
+        ev["metadata"]["no_speech_prob"] = no_speech_prob
+    return ev
 
 
 @dataclass
 class Hypothesis:
     """One recognition pass: the full transcript's token ids (forced prefix included) and text;
     from a pass that was asked for them, the words (asr/words.py, seconds from the utterance's
-    start) and the transcript's confidence."""
+    start) and the transcript's confidence; from an engine that analysed the start-of-transcript
+    logits, the language the pass decoded under, its probability and the probability that the
+    window holds no speech."""
 
     tokens: List[int] = field(default_factory=list)
     text: str = ""
     words: List[Dict] = field(default_factory=list)
     confidence: float = 0.0
+    language: Optional[str] = None
+    language_confidence: Optional[float] = None
+    no_speech_prob: Optional[float] = None
 
 
 class TextRecognizer:
@@ -118,8 +134,23 @@ class StreamingAsrSession:
                  partial_every_s: float = 1.0, endpoint_silence_s: Optional[float] = None,
                  energy_threshold: Optional[float] = None, max_window_s: float = 30.0, min_speech_s: float = 0.2,
                  local_agreement: bool = True, spec_silence_s: Optional[float] = None,
-                 noise_mult: Optional[float] = None, words: Optional[bool] = None):
+                 noise_mult: Optional[float] = None, words: Optional[bool] = None, language: Optional[str] = None,
+                 no_speech_threshold: Optional[float] = None):
         from ..utils.env import knob
+
+        # language (VWA_ASR_LANGUAGE): a code, or "auto" -- then the passes of an utterance ask the
+        # recognizer for "auto" until the first pass that commits tokens by local agreement; that
+        # pass's language is locked for the rest of the utterance, so a forced prefix is never
+        # decoded under another language token.  Set (by argument, or a knob other than "en"), the
+        # passes carry language= and the events the language; unset, neither (recognizers with the
+        # old signature keep working).
+        lang = str(knob("VWA_ASR_LANGUAGE") if language is None else language).strip().lower()
+        self.language: Optional[str] = lang if (language is not None or lang != "en") else None
+        self._lang_lock: Optional[str] = None
+        # no-speech gate (VWA_ASR_NO_SPEECH; 0: off): a pass whose no-speech probability exceeds it
+        # commits nothing and shows nothing -- its final is an empty transcript
+        self.no_speech_threshold = float(knob("VWA_ASR_NO_SPEECH") if no_speech_threshold is None
+                                         else no_speech_threshold)
 
         # word timestamps + confidences on final results (VWA_ASR_WORDS): the final pass and the
         # speculative final pass -- whose hypothesis becomes the final -- are asked for them
@@ -160,7 +191,7 @@ class StreamingAsrSession:
         self.prev_tokens: List[int] = []  # previous interim hypothesis
         self.stats: Dict[str, float] = {"partials": 0, "finals": 0, "asr_ms": 0.0, "passes": 0,
                                         "committed_tokens": 0, "spec_started": 0, "spec_used": 0,
-                                        "spec_discarded": 0}
+                                        "spec_discarded": 0, "no_speech": 0}
         # on_speculative(text): called (from the recognizer's thread) when a speculative final pass
         # finishes while it still covers the utterance -- the voice server starts the brain on it
         # (voice/server.py: the brain's latency then overlaps the rest of the endpoint wait)
@@ -181,9 +212,26 @@ class StreamingAsrSession:
         self._pcm[self._n : self._n + len(fr)] = fr
         self._n += len(fr)
 
+    def _pass_kw(self, final: bool) -> Dict:
+        """Keywords of a recognition pass: only those of the features that are on."""
+        kw: Dict[str, Any] = {"words": True} if final and self.words else {}
+        if self.language is not None:
+            kw["language"] = self._lang_lock or self.language
+        return kw
+
+    def _gated(self, hyp: Hypothesis) -> bool:
+        p = getattr(hyp, "no_speech_prob", None)
+        return self.no_speech_threshold > 0.0 and p is not None and p > self.no_speech_threshold
+
+    def _lang_kw(self, hyp: Hypothesis) -> Dict:
+        lang = getattr(hyp, "language", None) if self.language is not None else None
+        if lang is None:
+            return {}
+        return dict(language=lang, language_confidence=getattr(hyp, "language_confidence", None))
+
     def _run(self, final: bool = False) -> Hypothesis:
         t0 = time.perf_counter()
-        kw = {"words": True} if final and self.words else {}
+        kw = self._pass_kw(final)
         hyp = self.rec.recognize(self.buf, self.committed if self.local_agreement else (), **kw)
         self.stats["asr_ms"] += (time.perf_counter() - t0) * 1e3
         self.stats["passes"] += 1
@@ -216,6 +264,7 @@ class StreamingAsrSession:
         self.last_partial = ""
         self.committed = []
         self.prev_tokens = []
+        self._lang_lock = None
         self._drop_spec()
 
     def _drop_spec(self) -> None:
@@ -228,7 +277,7 @@ class StreamingAsrSession:
         self.stats["spec_started"] += 1
         self._spec_t0 = time.perf_counter()
         fut = recognize_async(self.rec, self.buf.copy(), self.committed if self.local_agreement else (),
-                              **({"words": True} if self.words else {}))
+                              **self._pass_kw(True))
         self._spec = fut
         if self.on_speculative is not None:
             fut.add_done_callback(self._spec_ready)
@@ -237,6 +286,8 @@ class StreamingAsrSession:
         if self._spec is not fut or fut.cancelled() or fut.exception() is not None:
             return  # (speech resumed meanwhile, or a failed pass: the endpoint runs the final itself)
         try:
+            if self._gated(fut.result()):
+                return  # (no speech in the window: nothing to start the brain on)
             self.on_speculative(fut.result().text)
         except Exception:  # noqa: BLE001  (a listener failure must not break recognition)
             pass
@@ -257,30 +308,39 @@ class StreamingAsrSession:
             if hyp is None:
                 hyp = self._run(final=True)
             kw = {}
-            if self.words:
+            text = hyp.text
+            if self._gated(hyp):
+                # Deepgram emits empty finals for noise too; the voice server drops an empty transcript
+                text, kw = "", dict(no_speech_prob=hyp.no_speech_prob)
+                self.stats["no_speech"] += 1
+            elif self.words:
                 kw = dict(confidence=getattr(hyp, "confidence", 0.0),
                           words=shift_words(getattr(hyp, "words", None) or [], self.t_offset))
-            out.append(results_event(hyp.text, is_final=True, start=self.t_offset, duration=len(self.buf) / self.rate,
-                                     model=self.model_name, **kw))
+            out.append(results_event(text, is_final=True, start=self.t_offset, duration=len(self.buf) / self.rate,
+                                     model=self.model_name, **kw, **self._lang_kw(hyp)))
             self.stats["finals"] += 1
         self._reset_utterance()
         return out
 
     def _partial(self) -> List[Dict]:
         hyp = self._run()
+        if self._gated(hyp):
+            return []  # (not speech: no event, nothing committed)
         if self.local_agreement and hyp.tokens:
             # LocalAgreement-2: what two consecutive hypotheses agree on is stable
             n = common_prefix(self.prev_tokens, hyp.tokens)
             if n > len(self.committed):
                 self.stats["committed_tokens"] += n - len(self.committed)
                 self.committed = list(hyp.tokens[:n])
+                if self.language == "auto" and self._lang_lock is None and getattr(hyp, "language", None):
+                    self._lang_lock = hyp.language  # the utterance's language from here on
             self.prev_tokens = list(hyp.tokens)
         if hyp.text == self.last_partial:
             return []
         self.last_partial = hyp.text
         self.stats["partials"] += 1
         return [results_event(hyp.text, is_final=False, start=self.t_offset, duration=len(self.buf) / self.rate,
-                              model=self.model_name)]
+                              model=self.model_name, **self._lang_kw(hyp))]
 
     # ------------------------------------------------------------------ API
     def push(self, data: bytes) -> List[Dict]:
@@ -352,13 +412,24 @@ def _words_knob(words: Optional[bool]) -> bool:
     return bool(knob("VWA_ASR_WORDS")) if words is None else bool(words)
 
 
-def _hypothesis(eng, full: List[int], n_samples: int, al=None) -> Hypothesis:
+def _hypothesis(eng, full: List[int], n_samples: int, al=None, sot: Optional[Dict] = None) -> Hypothesis:
     """The pass's hypothesis; with its alignment (a words pass) also the words, on the utterance's
-    own clock, and the transcript confidence (exp of the mean log-probability of its text tokens)."""
+    own clock, and the transcript confidence (exp of the mean log-probability of its text tokens);
+    with its ``last_sot`` entry the language and the no-speech probability."""
     text = eng.tok.decode(full).strip()
-    if al is None:
-        return Hypothesis(full, text)
-    return Hypothesis(full, text, eng.words_of(al, duration=n_samples / 16000.0), _confidence(al.logprobs))
+    hyp = Hypothesis(full, text)
+    if al is not None:
+        hyp.words, hyp.confidence = eng.words_of(al, duration=n_samples / 16000.0), _confidence(al.logprobs)
+    if sot is not None:
+        hyp.language, hyp.language_confidence = sot.get("language"), sot.get("language_confidence")
+        hyp.no_speech_prob = sot.get("no_speech_prob")
+    return hyp
+
+
+def _sot_of(eng, i: int) -> Optional[Dict]:
+    """Utterance i's start-of-transcript report of the engine's last call (engines without: None)."""
+    sots = getattr(eng, "last_sot", None)
+    return sots[i] if sots and i < len(sots) else None
 
 
 class EngineRecognizer:
@@ -371,12 +442,17 @@ class EngineRecognizer:
         self.max_tokens = max_tokens
         self.words = _words_knob(words)
 
-    def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False) -> Hypothesis:
+    def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
+                  language: Optional[str] = None) -> Hypothesis:
+        """language: this pass's language code or "auto" (None: the engine's default)."""
         prefix = list(prefix)[: self.eng.max_prefix()]  # the prefix the decoder actually forces
         words = bool(words) and self.words
-        toks = self.eng.decode_many([self.eng.pcm_to_audio(pcm)], [prefix], max_tokens=self.max_tokens,
-                                    **({"words": True} if words else {}))[0]
-        return _hypothesis(self.eng, prefix + toks, len(pcm), self.eng.last_alignments[0] if words else None)
+        kw = {"words": True} if words else {}
+        if language is not None:
+            kw["languages"] = [language]
+        toks = self.eng.decode_many([self.eng.pcm_to_audio(pcm)], [prefix], max_tokens=self.max_tokens, **kw)[0]
+        return _hypothesis(self.eng, prefix + toks, len(pcm), self.eng.last_alignments[0] if words else None,
+                           _sot_of(self.eng, 0))
 
 
 class AsrBatcher:
@@ -417,18 +493,21 @@ class AsrBatcher:
         self._thread = threading.Thread(target=self._loop, name="asr-batcher", daemon=True)
         self._thread.start()
 
-    def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False) -> Hypothesis:
-        return self.recognize_async(pcm, prefix, words=words).result()
+    def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
+                  language: Optional[str] = None) -> Hypothesis:
+        return self.recognize_async(pcm, prefix, words=words, language=language).result()
 
-    def recognize_async(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False) -> Future:
-        """Queue a pass for the next GPU batch; the Future resolves to its Hypothesis."""
+    def recognize_async(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
+                        language: Optional[str] = None) -> Future:
+        """Queue a pass for the next GPU batch; the Future resolves to its Hypothesis.  language:
+        this pass's code or "auto" (None: the engine's default); a batch may mix them."""
         fut: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("ASR batcher stopped")
             # (cut to what the decoder forces: the hypothesis is built on the prefix it really used)
             self._q.append((np.array(pcm, dtype=np.int16, copy=True), list(prefix)[: self.eng.max_prefix()], fut,
-                            bool(words) and self.words))
+                            bool(words) and self.words, language))
             self._cv.notify()
         return fut
 
@@ -456,20 +535,22 @@ class AsrBatcher:
             if self.busy is not None:
                 self.busy.enter()
             try:
-                audios = [self.eng.pcm_to_audio(p) for p, _, _, _ in batch]
+                audios = [self.eng.pcm_to_audio(p) for p, _, _, _, _ in batch]
                 kw = dict(max_tokens=self.max_tokens)
                 if self.tokens_per_s:
                     kw = dict(exact_tokens=max(1, min(self.max_tokens, max(
-                        int(round(len(p) / 16000 * self.tokens_per_s)) - len(pre) for p, pre, _, _ in batch))))
-                want = any(w for _, _, _, w in batch)
+                        int(round(len(p) / 16000 * self.tokens_per_s)) - len(pre) for p, pre, _, _, _ in batch))))
+                want = any(w for _, _, _, w, _ in batch)
                 if want:
                     kw["words"] = True
-                toks = self.eng.decode_many(audios, [pre for _, pre, _, _ in batch], **kw)
+                if any(l is not None for _, _, _, _, l in batch):
+                    kw["languages"] = [l for _, _, _, _, l in batch]
+                toks = self.eng.decode_many(audios, [pre for _, pre, _, _, _ in batch], **kw)
                 als = self.eng.last_alignments if want else [None] * len(batch)
-                for (p, pre, fut, w), t, al in zip(batch, toks, als):
-                    fut.set_result(_hypothesis(self.eng, pre + t, len(p), al if w else None))
+                for i, ((p, pre, fut, w, _), t, al) in enumerate(zip(batch, toks, als)):
+                    fut.set_result(_hypothesis(self.eng, pre + t, len(p), al if w else None, _sot_of(self.eng, i)))
             except BaseException as e:  # noqa: BLE001  (fail this batch's passes, keep serving)
-                for _, _, fut, _ in batch:
+                for _, _, fut, _, _ in batch:
                     if not fut.done():
                         fut.set_exception(e)
             finally:

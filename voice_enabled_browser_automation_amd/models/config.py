@@ -91,6 +91,20 @@ class WhisperConfig:
     def ffn(self) -> int:
         return 4 * self.d_model
 
+    # the special tokens around the two stored task ids (multilingual layout: the language tokens,
+    # <|translate|>, <|transcribe|>, <|startoflm|>, <|startofprev|>, <|nospeech|>, <|notimestamps|>)
+    @property
+    def translate(self) -> int:
+        return self.transcribe - 1
+
+    @property
+    def no_speech(self) -> int:
+        return self.no_timestamps - 1
+
+    @property
+    def n_langs(self) -> int:
+        return self.translate - self.lang_en
+
 
 LLAMA_PRESETS = {
     "llama3-8b": LlamaConfig(),

@@ -1262,3 +1262,83 @@ def env_flag(name: str) -> bool:
 
 def env_int(name: str) -> int:
     return int(knob(name))
+
+
+# ----------------------------------------------------------------------------- start-of-transcript probe
+_SOT = None
+_SOT_ERR: Optional[BaseException] = None
+SOT_MAX_LANGS = 128  # csrc/sot/sot.h kSotMaxLangs: one lane per language
+
+
+def sot_ext():
+    """Load the start-of-transcript probe library ``_vwa_sot.so`` (once). Raises if unavailable."""
+    global _SOT, _SOT_ERR
+    if _SOT is not None:
+        return _SOT
+    if _SOT_ERR is not None:
+        raise RuntimeError(f"native gfx950 SOT probe library unavailable: {_SOT_ERR}") from _SOT_ERR
+    try:
+        from . import _vwa_sot as m  # type: ignore
+
+        _SOT = m
+        return m
+    except BaseException as e:  # noqa: BLE001
+        _SOT_ERR = e
+        raise RuntimeError(
+            "native gfx950 SOT probe library _vwa_sot.so failed to load; build it with "
+            "`python -m voice_enabled_browser_automation_amd.ops.build`"
+        ) from e
+
+
+def sot_probe(logits: torch.Tensor, vocab: int, lang0: int, n_lang: int, no_speech_id: int,
+              allow: Optional[int] = None, *, lang_probs: Optional[torch.Tensor] = None,
+              lang_tok: Optional[torch.Tensor] = None, lang_conf: Optional[torch.Tensor] = None,
+              no_speech: Optional[torch.Tensor] = None, tok_dst: Optional[torch.Tensor] = None,
+              dst_rows: Optional[torch.Tensor] = None):
+    """What Whisper reads from the logits at the start-of-transcript position, per row of f32
+    ``logits`` [rows, >= vocab]: ``no_speech`` = the softmax over ids < vocab at ``no_speech_id``;
+    ``lang_probs`` [rows, >= n_lang] = the softmax over the allowed language ids ``lang0 + i``
+    (``allow``: an int whose bit i admits language i; None: all ``n_lang``), exactly 0 for the
+    others; ``lang_tok`` = the lowest allowed id whose raw logit is the maximum over the allowed ids
+    (always an allowed id); ``lang_conf`` = its probability.  With ``tok_dst`` / ``dst_rows`` (int32)
+    the id is also written to ``tok_dst[dst_rows[r]]`` for every ``0 <= dst_rows[r] < len(tok_dst)``
+    -- the detected language goes into the next decoder step's staged tokens without a host round
+    trip.  Returns (lang_probs, lang_tok, lang_conf, no_speech); one launch on the GPU."""
+    if logits.dim() != 2:
+        raise ValueError(f"sot_probe: logits must be [rows, >= vocab], not {tuple(logits.shape)}")
+    rows, ld = logits.shape
+    full = (1 << n_lang) - 1 if 1 <= n_lang <= SOT_MAX_LANGS else 0
+    allow = full if allow is None else int(allow)
+    if rows < 1:
+        raise ValueError("sot_probe: no rows")
+    if not 1 <= n_lang <= SOT_MAX_LANGS:
+        raise ValueError(f"sot_probe: n_lang = {n_lang} outside [1, {SOT_MAX_LANGS}]")
+    if lang0 < 0 or lang0 + n_lang > vocab:
+        raise ValueError(f"sot_probe: languages [{lang0}, {lang0 + n_lang}) outside the vocabulary [0, {vocab})")
+    if vocab > ld:
+        raise ValueError(f"sot_probe: vocab = {vocab} exceeds the logits' row length {ld}")
+    if not 0 <= no_speech_id < vocab:
+        raise ValueError(f"sot_probe: no_speech_id = {no_speech_id} outside [0, {vocab})")
+    if allow < 0 or allow & full == 0:
+        raise ValueError(f"sot_probe: allow = {allow:#x} admits no language below n_lang = {n_lang}")
+    allow &= full
+    dev = logits.device
+    if lang_probs is None:
+        lang_probs = torch.empty(rows, n_lang, dtype=torch.float32, device=dev)
+    if lang_probs.dim() != 2 or lang_probs.shape[0] < rows or lang_probs.shape[1] < n_lang:
+        raise ValueError(f"sot_probe: lang_probs {tuple(lang_probs.shape)} is smaller than [{rows}, {n_lang}]")
+    if lang_tok is None:
+        lang_tok = torch.empty(rows, dtype=torch.int32, device=dev)
+    if lang_conf is None:
+        lang_conf = torch.empty(rows, dtype=torch.float32, device=dev)
+    if no_speech is None:
+        no_speech = torch.empty(rows, dtype=torch.float32, device=dev)
+    if (tok_dst is None) != (dst_rows is None):
+        raise ValueError("sot_probe: tok_dst and dst_rows are given together or not at all")
+    if not _gpu(logits):
+        return ref.sot_probe(logits, vocab, lang0, n_lang, allow, no_speech_id, lang_probs, lang_tok, lang_conf,
+                             no_speech, tok_dst, dst_rows)
+    words = [(allow >> (32 * i)) & 0xFFFFFFFF for i in range(4)]
+    sot_ext().sot_probe(logits, vocab, lang0, n_lang, words, no_speech_id, lang_probs, lang_tok, lang_conf, no_speech,
+                        tok_dst, dst_rows)
+    return lang_probs, lang_tok, lang_conf, no_speech

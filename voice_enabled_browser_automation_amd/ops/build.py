@@ -6,6 +6,8 @@
   torch's own HIP runtime (same ``libamdhip64.so.7`` soname, so one HIP runtime per process).
 * ``_vwa_align.so`` -- the word-alignment kernels (``csrc/align/*.hip`` + its own ``bindings.cpp``),
   built and linked the same way into a library of its own.
+* ``_vwa_sot.so`` -- the start-of-transcript probe (``csrc/sot/*.hip`` + its own ``bindings.cpp``),
+  likewise.
 * ``_vwa_native.so`` -- the CPU runtime library (grammar engine, KV block manager): plain C++17
   with pybind11, built with g++.
 
@@ -31,6 +33,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 KERNEL_SO = os.path.join(HERE, "_vwa_kernels.so")
 NATIVE_SO = os.path.join(HERE, "_vwa_native.so")
 ALIGN_SO = os.path.join(HERE, "_vwa_align.so")
+SOT_SO = os.path.join(HERE, "_vwa_sot.so")
 
 
 def _torch_paths():
@@ -100,38 +103,48 @@ def build_kernels(force: bool = False, jobs: int = 8) -> str:
     return KERNEL_SO
 
 
-def build_align(force: bool = False, jobs: int = 8) -> str:
-    """Word-alignment kernel library: csrc/align/*.hip + csrc/align/bindings.cpp -> _vwa_align.so
-    (objects under build/native/align; the shared device helpers come from csrc/kernels/common.h)."""
-    bdir = os.path.join(BUILD, "align")
+def _build_kernel_lib(sub: str, so: str, ext_name: str, force: bool, jobs: int) -> str:
+    """A kernel library of its own: csrc/<sub>/*.hip + csrc/<sub>/bindings.cpp -> ``so`` (objects
+    under build/native/<sub>; the shared device helpers come from csrc/kernels/common.h)."""
+    bdir = os.path.join(BUILD, sub)
     os.makedirs(bdir, exist_ok=True)
     inc, lib, abi = _torch_paths()
-    headers = glob.glob(os.path.join(CSRC, "align", "*.h")) + [os.path.join(CSRC, "kernels", "common.h")]
+    headers = glob.glob(os.path.join(CSRC, sub, "*.h")) + [os.path.join(CSRC, "kernels", "common.h")]
     common = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result",
               "-I", os.path.join(CSRC)] + os.environ.get("VWA_HIPCC_EXTRA", "").split()
     jobs_list = []
     objs = []
-    for src in sorted(glob.glob(os.path.join(CSRC, "align", "*.hip"))):
+    for src in sorted(glob.glob(os.path.join(CSRC, sub, "*.hip"))):
         obj = os.path.join(bdir, os.path.basename(src) + ".o")
         objs.append(obj)
         if force or not _newer(obj, [src] + headers):
             jobs_list.append(common + ["-c", src, "-o", obj])
-    bind_src = os.path.join(CSRC, "align", "bindings.cpp")
+    bind_src = os.path.join(CSRC, sub, "bindings.cpp")
     bind_obj = os.path.join(bdir, "bindings.o")
     objs.append(bind_obj)
     if force or not _newer(bind_obj, [bind_src] + headers):
         cmd = common + ["-c", bind_src, "-o", bind_obj, f"-D_GLIBCXX_USE_CXX11_ABI={abi}",
-                        "-DTORCH_EXTENSION_NAME=_vwa_align", "-DUSE_ROCM=1", "-I", _py_include()]
+                        f"-DTORCH_EXTENSION_NAME={ext_name}", "-DUSE_ROCM=1", "-I", _py_include()]
         for i in inc:
             cmd += ["-I", i]
         jobs_list.append(cmd)
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
         list(ex.map(_run, jobs_list))
-    if force or jobs_list or not _newer(ALIGN_SO, objs):
-        _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", ALIGN_SO] + objs + [
+    if force or jobs_list or not _newer(so, objs):
+        _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", so] + objs + [
             "-L", lib, "-ltorch", "-ltorch_cpu", "-ltorch_python", "-lc10", "-lc10_hip", "-ltorch_hip",
             f"-Wl,-rpath,{lib}"])
-    return ALIGN_SO
+    return so
+
+
+def build_align(force: bool = False, jobs: int = 8) -> str:
+    """Word-alignment kernel library: csrc/align -> _vwa_align.so."""
+    return _build_kernel_lib("align", ALIGN_SO, "_vwa_align", force, jobs)
+
+
+def build_sot(force: bool = False, jobs: int = 8) -> str:
+    """Start-of-transcript probe library (language detection, no-speech gate): csrc/sot -> _vwa_sot.so."""
+    return _build_kernel_lib("sot", SOT_SO, "_vwa_sot", force, jobs)
 
 
 def build_native(force: bool = False) -> str:
@@ -156,6 +169,7 @@ def build_all(force: bool = False) -> list[str]:
         out.append(n)
     out.append(build_kernels(force))
     out.append(build_align(force))
+    out.append(build_sot(force))
     return out
 
 

@@ -412,3 +412,32 @@ def token_logprob(logits, targets, mask, vocab, out):
     t = targets[:N].long().clamp(0, vocab - 1)
     out[:N] = (x.gather(1, t[:, None])[:, 0] - torch.logsumexp(x, dim=-1)).clamp_max(0.0)
     return out
+
+
+def sot_probe(logits, vocab, lang0, n_lang, allow, no_speech_id, lang_probs, lang_tok, lang_conf, no_speech,
+              tok_dst=None, dst_rows=None):
+    """Start-of-transcript probe (csrc/sot/sot.h): per row the softmax over ids < vocab at
+    no_speech_id, the softmax over the allowed language ids (allow: int bit set, bit i = language
+    lang0 + i; exactly 0 elsewhere), the lowest allowed id holding the raw maximum (an id of the set
+    whatever the logits hold), its probability, and the token patch tok_dst[dst_rows[r]] = id."""
+    R = logits.shape[0]
+    x = logits[:, :vocab].float()
+    no_speech[:R] = torch.softmax(x, dim=-1)[:, no_speech_id]
+    on = torch.tensor([(allow >> i) & 1 == 1 for i in range(n_lang)])
+    xl = x[:, lang0 : lang0 + n_lang].masked_fill(~on, float("-inf"))
+    ml = torch.nan_to_num(xl, nan=float("-inf")).amax(dim=-1, keepdim=True)
+    e = torch.exp(xl - ml)  # (every allowed logit -inf: NaN, as the kernel gives)
+    p = torch.where(on, e / torch.where(on, e, torch.zeros(())).sum(-1, keepdim=True), torch.zeros(()))
+    lang_probs[:R, :n_lang] = p
+    idx = torch.arange(n_lang)
+    hit = on & (xl == ml)
+    best = torch.where(hit, idx, n_lang).amin(dim=-1)
+    best = torch.where(best == n_lang, int(idx[on][0]), best)
+    lang_tok[:R] = (lang0 + best).to(lang_tok.dtype)
+    lang_conf[:R] = p.gather(1, best[:, None])[:, 0]
+    if tok_dst is not None:
+        for r in range(R):
+            d = int(dst_rows[r])
+            if 0 <= d < tok_dst.numel():
+                tok_dst[d] = int(lang_tok[r])
+    return lang_probs, lang_tok, lang_conf, no_speech

@@ -61,16 +61,9 @@ def _iter_corpus(max_bytes: int):
 
 
 def whisper_special_tokens(n_vocab: int = 51865) -> list[str]:
-    langs = [
-        "en", "zh", "de", "es", "ru", "ko", "fr", "ja", "pt", "tr", "pl", "ca", "nl", "ar", "sv", "it", "id",
-        "hi", "fi", "vi", "he", "uk", "el", "ms", "cs", "ro", "da", "hu", "ta", "no", "th", "ur", "hr", "bg",
-        "lt", "la", "mi", "ml", "cy", "sk", "te", "fa", "lv", "bn", "sr", "az", "sl", "kn", "et", "mk", "br",
-        "eu", "is", "hy", "ne", "mn", "bs", "kk", "sq", "sw", "gl", "mr", "pa", "si", "km", "sn", "yo", "so",
-        "af", "oc", "ka", "be", "tg", "sd", "gu", "am", "yi", "lo", "uz", "fo", "ht", "ps", "tk", "nn", "mt",
-        "sa", "lb", "my", "bo", "tl", "mg", "as", "tt", "haw", "ln", "ha", "ba", "jw", "su",
-    ]
-    if n_vocab == 51866:
-        langs = langs + ["yue"]
+    from .languages import language_codes
+
+    langs = list(language_codes(100 if n_vocab == 51866 else 99))
     toks = ["<|endoftext|>", "<|startoftranscript|>"] + [f"<|{l}|>" for l in langs]
     toks += ["<|translate|>", "<|transcribe|>", "<|startoflm|>", "<|startofprev|>", "<|nospeech|>", "<|notimestamps|>"]
     toks += [f"<|{i * 0.02:.2f}|>" for i in range(1501)]

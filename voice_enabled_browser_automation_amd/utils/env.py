@@ -114,6 +114,10 @@ class Settings(BaseModel):
     VWA_PARTIAL_EVERY_S: float = Field(1.0, description="interim result period during speech")
     VWA_ASR_TOKENS_PER_S: float = Field(0.0, description="fixed-work transcripts (benchmarks on random weights; 0: off)")
     VWA_ASR_WORDS: bool = Field(False, description="final transcript events carry per-word start / end / confidence and the transcript confidence (an alignment pass after each final recognition pass: csrc/align)")
+    VWA_ASR_LANGUAGE: str = Field("en", description="spoken language of the recognizer: a Whisper language code, or auto (detected per utterance from the logits at the start-of-transcript position: csrc/sot; one extra one-row decoder step per pass)")
+    VWA_ASR_LANGUAGES: Optional[str] = Field(None, description="comma list of language codes that detection may report (unset: every language of the model)")
+    VWA_ASR_TASK: str = Field("transcribe", description="Whisper task: transcribe | translate (to English)")
+    VWA_ASR_NO_SPEECH: float = Field(0.0, description="no-speech gate: a window whose no-speech probability exceeds this yields an empty final and no partial (0: off; Whisper's customary threshold is 0.6)")
     VWA_CONTEXT_MAX_BYTES: int = Field(2048, description="per-session context cap sent to the brain")
     # ---- engine
     VWA_HIPGRAPH: bool = Field(True, description="replay decode steps from captured hipGraphs")
