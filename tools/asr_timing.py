@@ -4,6 +4,7 @@ bench's synthetic 10 s utterance.  One JSON line per mode.
 python tools/asr_timing.py [--asr whisper-large-v3] [--reps 10]
 python tools/asr_timing.py --words [--asr whisper-large-v3]   # the final pass without / with word timestamps
 python tools/asr_timing.py --language auto [--asr whisper-large-v3]   # the pass with a fixed / a detected language
+python tools/asr_timing.py --beam 5 [--asr whisper-large-v3]   # beam search against W greedy rows, per token step
 
 decode_us_per_token = host time from the encoder's launch to the last token / tokens (includes the
 encoder and cross K/V projections still running after their launch); decode_gpu_us_per_token = the
@@ -40,6 +41,9 @@ def main():
     ap.add_argument("--language", default=None,
                     help="time the same pass with the default fixed language and with this one (auto: detected from "
                          "the start-of-transcript logits, one more one-row decoder step and the probe)")
+    ap.add_argument("--beam", type=int, default=0,
+                    help="time beam search of this width: per token step the select, the K/V gather and the whole "
+                         "step, beside the same number of sessions decoded greedily as W independent rows")
     ap.add_argument("--small-max-m", type=int, default=None,
                     help="A/B: rows up to which small weights take the one-tile kernel (16: the tiled GEMM above 16)")
     a = ap.parse_args()
@@ -88,6 +92,53 @@ def main():
                                   total_ms_q3=round(q[2], 3), align_ms=round(statistics.median(al), 3),
                                   align_heads=m.align_layers()[1])), flush=True)
         print(json.dumps(dict(tool="asr_timing", asr=a.asr, same_tokens=toks[False] == toks[True])), flush=True)
+        return
+    if a.beam:  # one utterance with W beams against W sessions decoded greedily (decode_many(beam_size=))
+        W = a.beam
+        eng = AsrEngine(m, load_tokenizer("whisper"), max_sessions=W)
+        audio = eng.pcm_to_audio(synth_speech(10.0, seed=100))
+        P = len(eng.prompt)
+
+        def timed(fn):
+            fn()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+            for e0, e1 in ev:
+                e0.record()
+                fn()
+                e1.record()
+            torch.cuda.synchronize()
+            return statistics.median(e0.elapsed_time(e1) for e0, e1 in ev) * 1e3
+
+        # the two kernels alone, at the context of the pass's last step (event-timed, one call each)
+        b = eng.runner.b
+        i32 = dict(dtype=torch.int32, device="cuda")
+        cum = -torch.rand(W, device="cuda")
+        logits = torch.randn(W, m.vocab_padded, device="cuda") * 3
+        select_us = timed(lambda: ops.beam_select(logits, cum, eng.mask_text, m.cfg.vocab_size, W))
+        slots = torch.arange(W, **i32)[None].contiguous()
+        parents = ((torch.arange(W, **i32) + 1) % W)[None].contiguous()  # every beam moves
+        n_ctx = torch.tensor([P + a.tokens], **i32)
+        gather_us = timed(lambda: ops.kv_beam_gather(b.k_cache, b.v_cache, b.block_table, slots, parents, n_ctx,
+                                                     max_ctx=P + a.tokens))
+        res = {}
+        for kind in ("greedy_rows", "beam", "greedy_rows", "beam"):  # interleaved, reps each
+            kw = dict(beam_size=W) if kind == "beam" else {}
+            batch = [audio] if kind == "beam" else [audio] * W
+            for _ in range(2):
+                eng.decode_many(batch, exact_tokens=a.tokens, **kw)
+            dgpu, bms = [], []
+            for _ in range(a.reps):
+                eng.decode_many(batch, exact_tokens=a.tokens, **kw)
+                dgpu.append(eng.last_stats.get("decode_gpu_ms") or 0.0)
+                bms.append(eng.last_stats.get("beam_ms") or 0.0)
+            res[kind] = (statistics.median(dgpu) * 1e3 / a.tokens, statistics.median(bms) * 1e3 / a.tokens)
+        g, bm = res["greedy_rows"][0], res["beam"]
+        print(json.dumps(dict(tool="asr_timing", asr=a.asr, beam=W, tokens=a.tokens, reps=a.reps,
+                              context=P + a.tokens, select_us=round(select_us, 1), gather_us=round(gather_us, 1),
+                              beam_step_us=round(bm[0], 1), beam_ops_and_copies_us_per_step=round(bm[1], 1),
+                              greedy_rows_step_us=round(g, 1),
+                              kernels_share_of_greedy_step=round((select_us + gather_us) / g, 4),
+                              step_overhead_share=round(bm[0] / g - 1.0, 4))), flush=True)
         return
     if a.language:  # the pass with the fixed default language and with --language (decode_many(languages=))
         eng = AsrEngine(m, load_tokenizer("whisper"), max_sessions=2)

@@ -18,6 +18,7 @@ import torch
 from .. import ops
 from ..models.whisper import WhisperModel
 from ..tokenizer.languages import language_code, language_index, language_token
+from . import beam as beam_rule
 from .words import Alignment, group_words
 
 BUCKETS = (1, 2, 4, 8, 16, 32, 64)
@@ -215,9 +216,14 @@ class AsrEngine:
         self.last_stats: Dict[str, float] = {}
         # decode_many(words=True): one entry per utterance of the last call (asr/words.py Alignment)
         self.last_alignments: List[Alignment] = []
+        # decode_many(beam_size >= 2): per utterance its ranked hypotheses {tokens, sum_logprob, avg_logprob};
+        # with keep_beam_trace also one entry per step of the last call (_decode_beams)
+        self.last_beams: List[List[Dict]] = []
+        self.last_beam_trace: List[Dict] = []
         self.free_slots = list(range(max_sessions - 1, -1, -1))
 
     keep_sot = False  # decode_many: always probe; keep host copies of the SOT logits and language probabilities
+    keep_beam_trace = False  # decode_many with beams: keep host copies of every step's select inputs and outputs
 
     def _task_id(self, task: str) -> int:
         cfg = self.model.cfg
@@ -369,7 +375,7 @@ class AsrEngine:
     def decode_many(self, audios: List[torch.Tensor], prefixes: Optional[Sequence[Sequence[int]]] = None, *,
                     max_tokens: int = 96, min_tokens: int = 0, exact_tokens: Optional[int] = None,
                     words: bool = False, languages: Optional[Sequence[Optional[str]]] = None,
-                    task: Optional[str] = None) -> List[List[int]]:
+                    task: Optional[str] = None, beam_size: int = 1) -> List[List[int]]:
         """Token ids decoded for each utterance.  ``prefixes[i]``: text tokens forced after the
         SOT sequence (a streaming session's committed transcript -- asr/streaming.py local
         agreement): they are prefilled in the same ragged prompt step as the SOT tokens and only
@@ -387,12 +393,25 @@ class AsrEngine:
         language used, and -- when a session is "auto", the no-speech gate is on or ``keep_sot`` is
         set -- its confidence and the no-speech probability (``_probe``).  With every language fixed
         and the gate off nothing is launched for it; a gated session is still decoded (skipping it
-        would take a host wait on every un-gated call)."""
+        would take a host wait on every un-gated call).
+
+        ``beam_size`` W >= 2 (<= 8): every utterance is decoded with W beams (_decode_beams) and the
+        best hypothesis' tokens are returned; ``self.last_beams[i]`` holds utterance i's ranked
+        hypotheses.  An utterance takes W session slots for the call -- the encoder and the cross K/V
+        are computed once, into the first; the others' ``cross_table`` rows point at it and are
+        restored when the call ends -- so B * W free slots (<= 64) are needed.  1: the greedy path,
+        and nothing of the beam library is loaded or launched."""
         t0 = time.perf_counter()
         m = self.model
         B = len(audios)
+        W = int(beam_size)
+        if W != 1 and not 2 <= W <= ops.BEAM_MAX_WIDTH:
+            raise ValueError(f"beam_size = {beam_size} outside [1, {ops.BEAM_MAX_WIDTH}]")
         if B > len(self.free_slots):
             raise RuntimeError(f"{B} utterances exceed the {len(self.free_slots)} free ASR session slots")
+        if W > 1 and (B * W > len(self.free_slots) or B * W > ops.BEAM_MAX_ROWS):
+            raise RuntimeError(f"{B} utterances of {W} beams exceed the {min(len(self.free_slots), ops.BEAM_MAX_ROWS)} "
+                               "free ASR session slots")
         prefixes = [list(p) for p in prefixes] if prefixes is not None else [[] for _ in range(B)]
         assert len(prefixes) == B
         r = self.runner
@@ -409,8 +428,17 @@ class AsrEngine:
         probe = any(auto) or self.no_speech_threshold > 0.0 or self.keep_sot
         sot = None
         slots = [self.free_slots.pop() for _ in range(B)]
+        # beams: utterance i's beams sit in slots[i] (beam 0: prompt, encoder K/V, alignment) and W - 1 more
+        beam_slots = [[s] + [self.free_slots.pop() for _ in range(W - 1)] for s in slots] if W > 1 else None
+        cross_saved = None
         retry = False
         try:
+            if beam_slots is not None:
+                ct = r.b.cross_table
+                cross_saved = ct.clone()
+                extra = torch.tensor([s for bs_ in beam_slots for s in bs_[1:]], dtype=torch.long, device=ct.device)
+                first = torch.tensor([bs_[0] for bs_ in beam_slots for _ in bs_[1:]], dtype=torch.long, device=ct.device)
+                ct[extra] = ct[first]  # every beam reads the utterance's one cross K/V
             mel = m.mel_batch(audios)
             enc = m.encode(mel)
             self.set_cross_batch(slots, enc)
@@ -435,7 +463,12 @@ class AsrEngine:
             n_max = exact_tokens if exact_tokens is not None else max_tokens
             pos = [len(p) for p in prompts]  # next position per session
             limit = [min(n_max, cap - len(p)) for p in prompts]
-            if B == 1 and self.device_loop and (exact_tokens is not None or min_tokens == 0) and n_max > 0:
+            beam_ms = None
+            if beam_slots is not None:
+                outs, beam_ms = self._decode_beams(beam_slots, logits, pos, limit, n_max, min_tokens,
+                                                   exact_tokens is not None)
+                live = []
+            elif B == 1 and self.device_loop and (exact_tokens is not None or min_tokens == 0) and n_max > 0:
                 outs[0] = self._decode_device(slots[0], logits, limit[0], exact_tokens is not None, P=pos[0])
                 live = []
             for i in range(n_max if live else 0):
@@ -464,6 +497,10 @@ class AsrEngine:
                                    decode_gpu_ms=dec_gpu, total_ms=(t_end - t0) * 1e3,
                                    tokens=sum(len(o) for o in outs), batch=B,
                                    prefix_tokens=sum(len(p) - len(self.prompt) for p in prompts))
+            if beam_slots is not None:
+                self.last_stats["beam_size"] = W
+                if beam_ms is not None:
+                    self.last_stats["beam_ms"] = beam_ms()
             if not retry:
                 self.last_sot = self._read_sot(sot, langs, prompts)  # (fills in the detected language tokens)
                 if words:
@@ -472,9 +509,131 @@ class AsrEngine:
                     self.last_stats["align_ms"] = (time.perf_counter() - t_end) * 1e3
                 return outs
         finally:
-            self.free_slots.extend(slots)
+            if beam_slots is None:
+                self.free_slots.extend(slots)
+            else:
+                if cross_saved is not None:
+                    r.b.cross_table.copy_(cross_saved)
+                # (in reverse: the free list is what it was before the call)
+                self.free_slots.extend(reversed(slots + [s for bs_ in beam_slots for s in bs_[1:]]))
         return self.decode_many(audios, prefixes, max_tokens=max_tokens, min_tokens=min_tokens,
-                                exact_tokens=exact_tokens, words=words, languages=languages, task=task)
+                                exact_tokens=exact_tokens, words=words, languages=languages, task=task,
+                                beam_size=beam_size)
+
+    def _decode_beams(self, beam_slots: List[List[int]], logits: torch.Tensor, pos: List[int], limit: List[int],
+                      n_max: int, min_tokens: int, exact: bool):
+        """Beam search over every utterance of the call in one batch.  ``logits``: each utterance's
+        last prompt row (the prompt is prefilled on beam 0's slot only); ``pos[i]``: utterance i's
+        prompt length.  Per token step:
+
+        1. ops.beam_select over the W rows of every live utterance (the first step with cum =
+           [0, -inf, ...]: only beam 0's row counts);
+        2. ONE device-to-host copy of the packed candidates;
+        3. the bookkeeping (asr/beam.py advance) -- a finished utterance drops out;
+        4. ONE host-to-device copy: the live groups' slots, parents, context lengths and new cum;
+        5. ops.kv_beam_gather over the positions below the current one (the first one, with every
+           parent 0, fans the prompt's K/V out to all beams);
+        6. runner.step with W rows per live utterance.
+
+        Returns (the best hypothesis' tokens per utterance, a callable giving the event-timed
+        milliseconds of select, gather and the copies -- None on the CPU); fills ``last_beams`` and,
+        with ``keep_beam_trace``, ``last_beam_trace``: per step ``utts`` (the live utterances, in row
+        order), ``logits`` [G W, vocab_padded] and ``cum`` [G, W] the select read, ``allow_eot`` (the
+        mask: text ids with or without EOT), ``cand_score`` / ``cand_beam`` / ``cand_tok`` [G, 2 W],
+        and ``parents`` / ``tokens`` [G, W] chosen."""
+        m = self.model
+        cfg = m.cfg
+        r = self.runner
+        b = r.b
+        dev = m.device
+        cuda = dev.type == "cuda"
+        B, W = len(beam_slots), len(beam_slots[0])
+        K = 2 * W
+        states = [beam_rule.BeamState(W, cfg.eot, limit[i]) for i in range(B)]
+        live = [i for i in range(B) if not states[i].done]
+        x = torch.zeros(B * W, logits.shape[1], dtype=torch.float32, device=dev)
+        x[0::W] = logits  # (the dead rows are never read into a result: any finite filler serves)
+        if live != list(range(B)):
+            x = x.view(B, W, -1)[live].reshape(len(live) * W, -1)
+        res = torch.empty(3 * B * K, dtype=torch.float32, device=dev)  # score | beam | token, per step [3, G, K]
+        n_stage = B * (3 * W + 1)
+        h_stage = torch.zeros(n_stage, dtype=torch.int32, pin_memory=cuda)  # slots | parents | cum bits | n_ctx
+        d_stage = torch.zeros(n_stage, dtype=torch.int32, device=dev)
+        timed: List[Tuple["torch.cuda.Event", "torch.cuda.Event"]] = []
+
+        def mark():
+            if not cuda:
+                return None
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            return e
+
+        def stage(groups: List[int], parents: List[List[int]], n_ctx: List[int]):
+            G = len(groups)
+            hs = h_stage[: G * (3 * W + 1)]
+            hs[: G * W] = torch.tensor([s for j in groups for s in beam_slots[j]], dtype=torch.int32)
+            hs[G * W : 2 * G * W] = torch.tensor(parents, dtype=torch.int32).reshape(-1)
+            hs[2 * G * W : 3 * G * W] = torch.tensor([c for j in groups for c in states[j].cum],
+                                                     dtype=torch.float32).view(torch.int32)
+            hs[3 * G * W :] = torch.tensor(n_ctx, dtype=torch.int32)
+            ds = d_stage[: G * (3 * W + 1)]
+            ds.copy_(hs, non_blocking=True)
+            return (ds[: G * W].view(G, W), ds[G * W : 2 * G * W].view(G, W),
+                    ds[2 * G * W : 3 * G * W].view(torch.float32), ds[3 * G * W :])
+
+        trace: List[Dict] = []
+        self.last_beam_trace = trace
+        t_a = mark()  # (the first select's bracket holds the first staging copy)
+        _, _, cum_d, _ = stage(live, [[0] * W for _ in live], [0] * len(live)) if live else (None,) * 4
+        for i in range(n_max):
+            if not live:
+                break
+            G = len(live)
+            allow_eot = not exact and i >= min_tokens
+            cs, cb, ct = (res[k * G * K : (k + 1) * G * K].view(G, K) for k in range(3))
+            ops.beam_select(x, cum_d, self.mask_text_eot if allow_eot else self.mask_text, cfg.vocab_size, W,
+                            cand_score=cs, cand_beam=cb.view(torch.int32), cand_tok=ct.view(torch.int32))
+            h = res[: 3 * G * K].cpu()  # the one copy (it also waits for the step)
+            if cuda:
+                timed.append((t_a, mark()))
+            hs = h[: G * K].view(G, K).tolist()
+            hb = h[G * K : 2 * G * K].view(torch.int32).view(G, K).tolist()
+            ht = h[2 * G * K :].view(torch.int32).view(G, K).tolist()
+            step = None
+            if self.keep_beam_trace:
+                step = dict(step=i, utts=list(live), logits=x.cpu().clone(), cum=[list(states[j].cum) for j in live],
+                            allow_eot=allow_eot, cand_score=h[: G * K].view(G, K).clone(),
+                            cand_beam=h[G * K : 2 * G * K].view(torch.int32).view(G, K).clone(),
+                            cand_tok=h[2 * G * K :].view(torch.int32).view(G, K).clone(), parents=[], tokens=[])
+                trace.append(step)
+            nxt, parents, tokens = [], [], []
+            for g, j in enumerate(live):
+                par, tok = beam_rule.advance(states[j], list(zip(hs[g], hb[g], ht[g])))
+                if step is not None:
+                    step["parents"].append(par)
+                    step["tokens"].append(tok)
+                if not states[j].done:
+                    nxt.append(j)
+                    parents.append(par)
+                    tokens.append(tok)
+            live = nxt
+            if not live:
+                break
+            t_c = mark()
+            n_ctx = [pos[j] + i for j in live]
+            slots_d, par_d, cum_d, ctx_d = stage(live, parents, n_ctx)
+            ops.kv_beam_gather(b.k_cache, b.v_cache, b.block_table, slots_d, par_d, ctx_d, max_ctx=max(n_ctx))
+            if cuda:
+                timed.append((t_c, mark()))  # (the forward that follows is not counted)
+            x = r.step([(beam_slots[j][w], tokens[g][w], pos[j] + i) for g, j in enumerate(live) for w in range(W)])
+            t_a = mark()
+        self.last_beams = [beam_rule.ranked(st) for st in states]
+        outs = [list(hyps[0]["tokens"]) for hyps in self.last_beams]
+
+        def beam_ms() -> float:
+            return float(sum(a.elapsed_time(z) for a, z in timed))
+
+        return outs, (beam_ms if cuda else None)
 
     keep_costs = False  # _align: also keep each utterance's cost matrix (host copy) in its Alignment
 

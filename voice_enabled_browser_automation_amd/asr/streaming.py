@@ -35,6 +35,7 @@ Events use the Deepgram ``Results`` shape that the unchanged UI and voice logic 
 """
 from __future__ import annotations
 
+import math
 import threading
 import time
 from concurrent.futures import Future
@@ -49,12 +50,15 @@ from .words import shift_words
 
 def results_event(text: str, *, is_final: bool, start: float, duration: float, model: str,
                   confidence: float = 0.0, words: Optional[List[Dict]] = None, language: Optional[str] = None,
-                  language_confidence: Optional[float] = None, no_speech_prob: Optional[float] = None) -> Dict:
+                  language_confidence: Optional[float] = None, no_speech_prob: Optional[float] = None,
+                  alternatives: Optional[List[Dict]] = None) -> Dict:
     """``words``: the alternative's Deepgram word list ({"word", "punctuated_word", "start", "end",
     "confidence"}, stream-clock seconds); None: the empty list.  ``language``: the detected (or
     set) language code -- Deepgram's ``channel.detected_language`` / ``language_confidence`` and
     the alternative's ``languages``.  ``no_speech_prob``: of a final the no-speech gate emptied
-    (``metadata.no_speech_prob``).  Without them the event is unchanged."""
+    (``metadata.no_speech_prob``).  ``alternatives``: the ranked hypotheses after the first
+    ({"transcript", "confidence"}, from a beam pass) -- ``channel.alternatives[1:]`` in Deepgram's
+    shape, with no words.  Without them the event is unchanged."""
     ev = {
         "type": "Results",
         "channel_index": [0, 1],
@@ -72,6 +76,9 @@ def results_event(text: str, *, is_final: bool, start: float, duration: float, m
         ev["channel"]["alternatives"][0]["languages"] = [language]
     if no_speech_prob is not None:
         ev["metadata"]["no_speech_prob"] = no_speech_prob
+    for alt in alternatives or []:
+        ev["channel"]["alternatives"].append({"transcript": alt["transcript"], "confidence": alt["confidence"],
+                                              "words": []})
     return ev
 
 
@@ -81,7 +88,9 @@ class Hypothesis:
     from a pass that was asked for them, the words (asr/words.py, seconds from the utterance's
     start) and the transcript's confidence; from an engine that analysed the start-of-transcript
     logits, the language the pass decoded under, its probability and the probability that the
-    window holds no speech."""
+    window holds no speech; from a beam pass, the ranked hypotheses after the first
+    (``alternatives``: {"transcript", "confidence" = exp(avg_logprob)}) -- ``confidence`` is then
+    the best hypothesis' exp(avg_logprob) unless the words pass set it."""
 
     tokens: List[int] = field(default_factory=list)
     text: str = ""
@@ -90,6 +99,7 @@ class Hypothesis:
     language: Optional[str] = None
     language_confidence: Optional[float] = None
     no_speech_prob: Optional[float] = None
+    alternatives: List[Dict] = field(default_factory=list)
 
 
 class TextRecognizer:
@@ -135,8 +145,14 @@ class StreamingAsrSession:
                  energy_threshold: Optional[float] = None, max_window_s: float = 30.0, min_speech_s: float = 0.2,
                  local_agreement: bool = True, spec_silence_s: Optional[float] = None,
                  noise_mult: Optional[float] = None, words: Optional[bool] = None, language: Optional[str] = None,
-                 no_speech_threshold: Optional[float] = None):
-        from ..utils.env import knob
+                 no_speech_threshold: Optional[float] = None, beam: Optional[int] = None,
+                 alternatives: Optional[int] = None):
+        from ..utils.env import asr_beam_knobs, knob
+
+        # beam search on the final passes (VWA_ASR_BEAM; 1: greedy) and the ranked alternatives a
+        # final event carries (VWA_ASR_ALTERNATIVES, 1..beam): the final pass and the speculative
+        # final pass are asked for recognize(..., beam=W); partials never are
+        self.beam, self.n_alternatives = asr_beam_knobs(beam, alternatives)
 
         # language (VWA_ASR_LANGUAGE): a code, or "auto" -- then the passes of an utterance ask the
         # recognizer for "auto" until the first pass that commits tokens by local agreement; that
@@ -215,6 +231,8 @@ class StreamingAsrSession:
     def _pass_kw(self, final: bool) -> Dict:
         """Keywords of a recognition pass: only those of the features that are on."""
         kw: Dict[str, Any] = {"words": True} if final and self.words else {}
+        if final and self.beam > 1:
+            kw["beam"] = self.beam
         if self.language is not None:
             kw["language"] = self._lang_lock or self.language
         return kw
@@ -316,6 +334,12 @@ class StreamingAsrSession:
             elif self.words:
                 kw = dict(confidence=getattr(hyp, "confidence", 0.0),
                           words=shift_words(getattr(hyp, "words", None) or [], self.t_offset))
+            if self.beam > 1 and not self._gated(hyp):
+                if not self.words:
+                    kw["confidence"] = getattr(hyp, "confidence", 0.0)  # exp(avg_logprob) of the best hypothesis
+                alts = list(getattr(hyp, "alternatives", None) or [])[: self.n_alternatives - 1]
+                if alts:
+                    kw["alternatives"] = alts
             out.append(results_event(text, is_final=True, start=self.t_offset, duration=len(self.buf) / self.rate,
                                      model=self.model_name, **kw, **self._lang_kw(hyp)))
             self.stats["finals"] += 1
@@ -412,12 +436,19 @@ def _words_knob(words: Optional[bool]) -> bool:
     return bool(knob("VWA_ASR_WORDS")) if words is None else bool(words)
 
 
-def _hypothesis(eng, full: List[int], n_samples: int, al=None, sot: Optional[Dict] = None) -> Hypothesis:
+def _hypothesis(eng, full: List[int], n_samples: int, al=None, sot: Optional[Dict] = None,
+                beams: Optional[List[Dict]] = None, prefix: Sequence[int] = ()) -> Hypothesis:
     """The pass's hypothesis; with its alignment (a words pass) also the words, on the utterance's
     own clock, and the transcript confidence (exp of the mean log-probability of its text tokens);
-    with its ``last_sot`` entry the language and the no-speech probability."""
+    with its ``last_sot`` entry the language and the no-speech probability; with its ``last_beams``
+    entry (a beam pass: ranked {tokens, sum_logprob, avg_logprob}, ``prefix`` the forced tokens
+    before them) the alternatives after the first and the confidence exp(avg_logprob) of the best."""
     text = eng.tok.decode(full).strip()
     hyp = Hypothesis(full, text)
+    if beams:
+        hyp.confidence = math.exp(beams[0]["avg_logprob"])
+        hyp.alternatives = [dict(transcript=eng.tok.decode(list(prefix) + list(h["tokens"])).strip(),
+                                 confidence=math.exp(h["avg_logprob"])) for h in beams[1:]]
     if al is not None:
         hyp.words, hyp.confidence = eng.words_of(al, duration=n_samples / 16000.0), _confidence(al.logprobs)
     if sot is not None:
@@ -443,16 +474,19 @@ class EngineRecognizer:
         self.words = _words_knob(words)
 
     def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
-                  language: Optional[str] = None) -> Hypothesis:
-        """language: this pass's language code or "auto" (None: the engine's default)."""
+                  language: Optional[str] = None, beam: int = 1) -> Hypothesis:
+        """language: this pass's language code or "auto" (None: the engine's default); beam: the
+        pass's beam width (1: greedy) -- it then takes that many of the engine's session slots."""
         prefix = list(prefix)[: self.eng.max_prefix()]  # the prefix the decoder actually forces
         words = bool(words) and self.words
         kw = {"words": True} if words else {}
         if language is not None:
             kw["languages"] = [language]
+        if beam > 1:
+            kw["beam_size"] = int(beam)
         toks = self.eng.decode_many([self.eng.pcm_to_audio(pcm)], [prefix], max_tokens=self.max_tokens, **kw)[0]
         return _hypothesis(self.eng, prefix + toks, len(pcm), self.eng.last_alignments[0] if words else None,
-                           _sot_of(self.eng, 0))
+                           _sot_of(self.eng, 0), self.eng.last_beams[0] if beam > 1 else None, prefix)
 
 
 class AsrBatcher:
@@ -494,22 +528,47 @@ class AsrBatcher:
         self._thread.start()
 
     def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
-                  language: Optional[str] = None) -> Hypothesis:
-        return self.recognize_async(pcm, prefix, words=words, language=language).result()
+                  language: Optional[str] = None, beam: int = 1) -> Hypothesis:
+        return self.recognize_async(pcm, prefix, words=words, language=language, beam=beam).result()
 
     def recognize_async(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
-                        language: Optional[str] = None) -> Future:
+                        language: Optional[str] = None, beam: int = 1) -> Future:
         """Queue a pass for the next GPU batch; the Future resolves to its Hypothesis.  language:
-        this pass's code or "auto" (None: the engine's default); a batch may mix them."""
+        this pass's code or "auto" (None: the engine's default); a batch may mix them.  beam: the
+        pass's beam width (1: greedy).  A beam pass counts ``beam`` session slots; greedy passes and
+        the beam passes of each width run as decode_many calls of their own, and a beam pass that
+        does not fit a round's slots stays queued for the next (it is never failed for that).  A
+        width the engine's slots can never hold is refused here."""
+        beam = int(beam)
+        if beam < 1 or beam > min(8, self.max_batch):
+            raise ValueError(f"beam = {beam} outside 1..{min(8, self.max_batch)} (the engine's session slots)")
         fut: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("ASR batcher stopped")
             # (cut to what the decoder forces: the hypothesis is built on the prefix it really used)
             self._q.append((np.array(pcm, dtype=np.int16, copy=True), list(prefix)[: self.eng.max_prefix()], fut,
-                            bool(words) and self.words, language))
+                            bool(words) and self.words, language, beam))
             self._cv.notify()
         return fut
+
+    def _take(self) -> Dict[int, List[tuple]]:
+        """(under the lock) The queued passes of this round by beam width, in queue order: of each
+        width as many as the slots hold (a pass of width W counts W; a beam call holds <= 64 rows);
+        the rest stays queued."""
+        groups: Dict[int, List[tuple]] = {}
+        used: Dict[int, int] = {}
+        rest: List[tuple] = []
+        for item in self._q:
+            w = item[5]
+            cap = self.max_batch if w == 1 else min(self.max_batch, 64)
+            if used.get(w, 0) + w <= cap:
+                groups.setdefault(w, []).append(item)
+                used[w] = used.get(w, 0) + w
+            else:
+                rest.append(item)
+        self._q = rest
+        return groups
 
     def rows_per_batch(self) -> float:
         return self.stats["passes"] / max(1, self.stats["batches"])
@@ -530,37 +589,47 @@ class AsrBatcher:
                     self._cv.wait()
                 if self._stop and not self._q:
                     return
-                batch, self._q = self._q[: self.max_batch], self._q[self.max_batch :]
-            t0 = time.perf_counter()
+                groups = self._take()
+            for width in sorted(groups):  # greedy passes first, then one call per beam width
+                self._run_batch(groups[width], width)
+
+    def _run_batch(self, batch: List[tuple], beam: int) -> None:
+        """One decode_many call: the round's greedy passes (beam 1) or its beam passes of one width."""
+        t0 = time.perf_counter()
+        if self.busy is not None:
+            self.busy.enter()
+        try:
+            audios = [self.eng.pcm_to_audio(item[0]) for item in batch]
+            kw = dict(max_tokens=self.max_tokens)
+            if self.tokens_per_s:
+                kw = dict(exact_tokens=max(1, min(self.max_tokens, max(
+                    int(round(len(item[0]) / 16000 * self.tokens_per_s)) - len(item[1]) for item in batch))))
+            want = any(item[3] for item in batch)
+            if want:
+                kw["words"] = True
+            if any(item[4] is not None for item in batch):
+                kw["languages"] = [item[4] for item in batch]
+            if beam > 1:
+                kw["beam_size"] = beam
+            toks = self.eng.decode_many(audios, [item[1] for item in batch], **kw)
+            als = self.eng.last_alignments if want else [None] * len(batch)
+            beams = self.eng.last_beams if beam > 1 else [None] * len(batch)
+            for i, (item, t, al) in enumerate(zip(batch, toks, als)):
+                p, pre, fut, w = item[:4]
+                fut.set_result(_hypothesis(self.eng, pre + t, len(p), al if w else None, _sot_of(self.eng, i),
+                                           beams[i], pre))
+        except BaseException as e:  # noqa: BLE001  (fail this batch's passes, keep serving)
+            for item in batch:
+                if not item[2].done():
+                    item[2].set_exception(e)
+        finally:
             if self.busy is not None:
-                self.busy.enter()
-            try:
-                audios = [self.eng.pcm_to_audio(p) for p, _, _, _, _ in batch]
-                kw = dict(max_tokens=self.max_tokens)
-                if self.tokens_per_s:
-                    kw = dict(exact_tokens=max(1, min(self.max_tokens, max(
-                        int(round(len(p) / 16000 * self.tokens_per_s)) - len(pre) for p, pre, _, _, _ in batch))))
-                want = any(w for _, _, _, w, _ in batch)
-                if want:
-                    kw["words"] = True
-                if any(l is not None for _, _, _, _, l in batch):
-                    kw["languages"] = [l for _, _, _, _, l in batch]
-                toks = self.eng.decode_many(audios, [pre for _, pre, _, _, _ in batch], **kw)
-                als = self.eng.last_alignments if want else [None] * len(batch)
-                for i, ((p, pre, fut, w, _), t, al) in enumerate(zip(batch, toks, als)):
-                    fut.set_result(_hypothesis(self.eng, pre + t, len(p), al if w else None, _sot_of(self.eng, i)))
-            except BaseException as e:  # noqa: BLE001  (fail this batch's passes, keep serving)
-                for _, _, fut, _, _ in batch:
-                    if not fut.done():
-                        fut.set_exception(e)
-            finally:
-                if self.busy is not None:
-                    self.busy.leave()
-            n = len(batch)
-            self.stats["batches"] += 1
-            self.stats["passes"] += n
-            self.stats["max_batch"] = max(self.stats["max_batch"], n)
-            self.stats["gpu_ms"] += (time.perf_counter() - t0) * 1e3
+                self.busy.leave()
+        n = len(batch)
+        self.stats["batches"] += 1
+        self.stats["passes"] += n
+        self.stats["max_batch"] = max(self.stats["max_batch"], n)
+        self.stats["gpu_ms"] += (time.perf_counter() - t0) * 1e3
 
     def close(self) -> None:
         with self._cv:

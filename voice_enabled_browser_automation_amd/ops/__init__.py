@@ -1342,3 +1342,147 @@ def sot_probe(logits: torch.Tensor, vocab: int, lang0: int, n_lang: int, no_spee
     sot_ext().sot_probe(logits, vocab, lang0, n_lang, words, no_speech_id, lang_probs, lang_tok, lang_conf, no_speech,
                         tok_dst, dst_rows)
     return lang_probs, lang_tok, lang_conf, no_speech
+
+
+# ----------------------------------------------------------------------------- beam search
+_BEAM = None
+_BEAM_ERR: Optional[BaseException] = None
+BEAM_MAX_WIDTH = 8        # csrc/beam/beam.h kBeamMaxWidth
+BEAM_MAX_ROWS = 64        # ... kBeamMaxRows: groups x beams per launch
+BEAM_MAX_VOCAB = 1 << 20  # ... kBeamMaxVocab
+
+
+def beam_ext():
+    """Load the beam search library ``_vwa_beam.so`` (once). Raises if unavailable."""
+    global _BEAM, _BEAM_ERR
+    if _BEAM is not None:
+        return _BEAM
+    if _BEAM_ERR is not None:
+        raise RuntimeError(f"native gfx950 beam search library unavailable: {_BEAM_ERR}") from _BEAM_ERR
+    try:
+        from . import _vwa_beam as m  # type: ignore
+
+        _BEAM = m
+        return m
+    except BaseException as e:  # noqa: BLE001
+        _BEAM_ERR = e
+        raise RuntimeError(
+            "native gfx950 beam search library _vwa_beam.so failed to load; build it with "
+            "`python -m voice_enabled_browser_automation_amd.ops.build`"
+        ) from e
+
+
+def _beam_width(what: str, rows: int, W: int) -> int:
+    """Groups of a [rows] = [G * W] launch (ValueError unless 2 <= W <= 8 and G * W <= 64)."""
+    if not 2 <= W <= BEAM_MAX_WIDTH:
+        raise ValueError(f"{what}: W = {W} beams outside [2, {BEAM_MAX_WIDTH}]")
+    if rows < W or rows % W or rows > BEAM_MAX_ROWS:
+        raise ValueError(f"{what}: {rows} rows are not 1..{BEAM_MAX_ROWS // W} groups of W = {W}")
+    return rows // W
+
+
+def beam_select(logits: torch.Tensor, cum: torch.Tensor, mask: Optional[torch.Tensor], vocab: int, W: int, *,
+                cand_score: Optional[torch.Tensor] = None, cand_beam: Optional[torch.Tensor] = None,
+                cand_tok: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """The best continuations of G groups of W beams (2 <= W <= 8, G * W <= 64): f32 ``logits``
+    [G * W, >= vocab], rows g * W .. g * W + W - 1 one group; f32 ``cum`` [G * W] the beams' running
+    log-probabilities (-inf: a dead row); ``mask`` the packed allow-mask [G * W or 1, words] of
+    ``token_logprob`` (None: all).  A candidate (beam b, id v) scores ``cum[row] + (x[v] - lse[row])``
+    in f32, ``lse`` over the row's allowed ids below ``vocab``.  Returns (cand_score f32, cand_beam
+    int32, cand_tok int32), each [G, 2 W]: per group the 2 W best finite scores in descending
+    order, equal scores by ascending ``b * vocab + v``; ranks past the group's candidates hold
+    (-inf, -1, -1).  Three launches on the GPU (csrc/beam/beam_select.hip); ``workspace``: int32
+    scratch of ``beam_ext().beam_select_workspace(rows, vocab) / 4`` elements (allocated when None)."""
+    if logits.dim() != 2:
+        raise ValueError(f"beam_select: logits must be [G * W, >= vocab], not {tuple(logits.shape)}")
+    N, ld = logits.shape
+    G = _beam_width("beam_select", N, int(W))
+    if not 1 <= vocab <= min(ld, BEAM_MAX_VOCAB):
+        raise ValueError(f"beam_select: vocab = {vocab} outside [1, {min(ld, BEAM_MAX_VOCAB)}] (the logits' row length)")
+    if logits.dtype != torch.float32 or cum.dtype != torch.float32:
+        raise ValueError(f"beam_select: logits and cum must be float32, not {logits.dtype} and {cum.dtype}")
+    if cum.dim() != 1 or cum.numel() < N:
+        raise ValueError(f"beam_select: cum must hold {N} scores, not {tuple(cum.shape)}")
+    if mask is not None:
+        if mask.dim() == 1:
+            mask = mask[None]
+        if mask.dtype != torch.int32 or mask.dim() != 2 or mask.shape[0] not in (1, N) or mask.shape[1] * 32 < vocab:
+            raise ValueError(f"beam_select: mask must be int32 [{N} or 1, >= {(vocab + 31) // 32}], not "
+                             f"{mask.dtype} {tuple(mask.shape)}")
+    K = 2 * W
+    dev = logits.device
+    if cand_score is None:
+        cand_score = torch.empty(G, K, dtype=torch.float32, device=dev)
+    if cand_beam is None:
+        cand_beam = torch.empty(G, K, dtype=torch.int32, device=dev)
+    if cand_tok is None:
+        cand_tok = torch.empty(G, K, dtype=torch.int32, device=dev)
+    for name, t, dt in (("cand_score", cand_score, torch.float32), ("cand_beam", cand_beam, torch.int32),
+                        ("cand_tok", cand_tok, torch.int32)):
+        if t.dtype != dt or t.dim() != 2 or t.shape[0] < G or t.shape[1] < K:
+            raise ValueError(f"beam_select: {name} must be {dt} [>= {G}, >= {K}], not {t.dtype} {tuple(t.shape)}")
+    if not _gpu(logits):
+        return ref.beam_select(logits, cum, mask, vocab, W, cand_score, cand_beam, cand_tok)
+    lib = beam_ext()  # (a missing library raises: there is no other GPU path)
+    if workspace is None:
+        workspace = scratch(dev, "beam_select", BEAM_MAX_ROWS * ((vocab + 8191) // 8192) * 34, torch.int32)
+    lib.beam_select(logits, cum, mask, vocab, W, cand_score, cand_beam, cand_tok, workspace)
+    return cand_score, cand_beam, cand_tok
+
+
+def kv_beam_gather(k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor, slots, parents,
+                   n_ctx, *, max_ctx: Optional[int] = None) -> None:
+    """The beams' self-attention K/V follow their new parents, in place and bitwise: caches bf16
+    [L, n_blocks, H, bs, hd] (the runner's layout), ``block_table`` int32 [sessions, bps], ``slots``
+    / ``parents`` int32 [G, W] (2 <= W <= 8, G * W <= 64; the session slot of each beam, distinct
+    within the call, and the index within the group of the beam it continues), ``n_ctx`` int32 [G]
+    the positions in context.  For every layer and block j < ceil(min(n_ctx[g], max_ctx) / bs) the
+    block of beam w receives the old content of beam parents[g][w]'s; parents may repeat and form
+    cycles; a beam that keeps its parent is not written, nor is anything else.  ``max_ctx`` bounds
+    the launch (None: the whole table).  Lists are checked here (ValueError) and copied to the
+    device; in device tensors an out-of-range slot or parent leaves its beam alone.  One launch
+    on the GPU (csrc/beam/kv_gather.hip, 16-byte loads and stores)."""
+    if k_cache.dim() != 5 or v_cache.shape != k_cache.shape:
+        raise ValueError(f"kv_beam_gather: caches must be [L, n_blocks, H, bs, hd], not {tuple(k_cache.shape)} and "
+                         f"{tuple(v_cache.shape)}")
+    if k_cache.dtype != torch.bfloat16 or v_cache.dtype != torch.bfloat16:
+        raise ValueError(f"kv_beam_gather: caches must be bfloat16, not {k_cache.dtype} and {v_cache.dtype}")
+    bs, hd = k_cache.shape[3], k_cache.shape[4]
+    if (bs * hd * 2) % 16:
+        raise ValueError(f"kv_beam_gather: a head's block ({bs} x {hd} bf16) is not a multiple of 16 bytes")
+    if block_table.dim() != 2 or block_table.dtype != torch.int32:
+        raise ValueError(f"kv_beam_gather: block_table must be int32 [sessions, bps], not {block_table.dtype} "
+                         f"{tuple(block_table.shape)}")
+    sessions, bps = block_table.shape
+    dev = k_cache.device
+
+    def grid(t, name, lo, hi):
+        if isinstance(t, torch.Tensor):
+            if t.dtype != torch.int32:
+                raise ValueError(f"kv_beam_gather: {name} must be int32, not {t.dtype}")
+            return t
+        t = torch.tensor(t, dtype=torch.int64)
+        if t.numel() and (int(t.min()) < lo or int(t.max()) >= hi):
+            raise ValueError(f"kv_beam_gather: {name} {t.tolist()} not all in [{lo}, {hi})")
+        return t.to(torch.int32).to(dev)
+
+    host_slots = None if isinstance(slots, torch.Tensor) else [int(s) for row in slots for s in row]
+    slots = grid(slots, "slots", 0, sessions)
+    if slots.dim() != 2:
+        raise ValueError(f"kv_beam_gather: slots must be [G, W], not {tuple(slots.shape)}")
+    G, W = slots.shape
+    _beam_width("kv_beam_gather", G * W, W)
+    if host_slots is not None and len(set(host_slots)) != len(host_slots):
+        raise ValueError(f"kv_beam_gather: slots {host_slots} repeat a session")
+    parents = grid(parents, "parents", 0, W)
+    n_ctx = grid(n_ctx, "n_ctx", 0, bps * bs + 1)
+    if tuple(parents.shape) != (G, W) or n_ctx.dim() != 1 or n_ctx.numel() < G:
+        raise ValueError(f"kv_beam_gather: parents {tuple(parents.shape)} / n_ctx {tuple(n_ctx.shape)} do not match "
+                         f"slots [{G}, {W}]")
+    max_ctx = bps * bs if max_ctx is None else int(max_ctx)
+    if not 0 <= max_ctx <= bps * bs:
+        raise ValueError(f"kv_beam_gather: max_ctx = {max_ctx} exceeds the block table's {bps} blocks of {bs} positions")
+    if not _gpu(k_cache):
+        ref.kv_beam_gather(k_cache, v_cache, block_table, slots, parents, n_ctx, max_ctx)
+        return
+    beam_ext().kv_beam_gather(k_cache, v_cache, block_table, slots.contiguous(), parents.contiguous(), n_ctx, max_ctx)

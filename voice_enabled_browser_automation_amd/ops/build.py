@@ -8,6 +8,7 @@
   built and linked the same way into a library of its own.
 * ``_vwa_sot.so`` -- the start-of-transcript probe (``csrc/sot/*.hip`` + its own ``bindings.cpp``),
   likewise.
+* ``_vwa_beam.so`` -- the beam search steps (``csrc/beam/*.hip`` + its own ``bindings.cpp``), likewise.
 * ``_vwa_native.so`` -- the CPU runtime library (grammar engine, KV block manager): plain C++17
   with pybind11, built with g++.
 
@@ -34,6 +35,7 @@ KERNEL_SO = os.path.join(HERE, "_vwa_kernels.so")
 NATIVE_SO = os.path.join(HERE, "_vwa_native.so")
 ALIGN_SO = os.path.join(HERE, "_vwa_align.so")
 SOT_SO = os.path.join(HERE, "_vwa_sot.so")
+BEAM_SO = os.path.join(HERE, "_vwa_beam.so")
 
 
 def _torch_paths():
@@ -147,6 +149,11 @@ def build_sot(force: bool = False, jobs: int = 8) -> str:
     return _build_kernel_lib("sot", SOT_SO, "_vwa_sot", force, jobs)
 
 
+def build_beam(force: bool = False, jobs: int = 8) -> str:
+    """Beam search library (candidate selection, K/V following the parents): csrc/beam -> _vwa_beam.so."""
+    return _build_kernel_lib("beam", BEAM_SO, "_vwa_beam", force, jobs)
+
+
 def build_native(force: bool = False) -> str:
     """CPU runtime library (grammar engine + block manager) -- g++ / pybind11."""
     srcs = sorted(glob.glob(os.path.join(CSRC, "runtime", "*.cpp")))
@@ -170,6 +177,7 @@ def build_all(force: bool = False) -> list[str]:
     out.append(build_kernels(force))
     out.append(build_align(force))
     out.append(build_sot(force))
+    out.append(build_beam(force))
     return out
 
 

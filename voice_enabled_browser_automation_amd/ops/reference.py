@@ -441,3 +441,62 @@ def sot_probe(logits, vocab, lang0, n_lang, allow, no_speech_id, lang_probs, lan
             if 0 <= d < tok_dst.numel():
                 tok_dst[d] = int(lang_tok[r])
     return lang_probs, lang_tok, lang_conf, no_speech
+
+
+def beam_select(logits, cum, mask, vocab, W, cand_score, cand_beam, cand_tok):
+    """Beam selection (csrc/beam/beam.h): rows are groups of W beams; a candidate (beam b, id v) of
+    a group scores cum[row] + (x[v] - lse[row]) in f32, lse over the allowed ids < vocab; per group
+    the 2 W best finite scores, descending, equal scores by ascending b * vocab + v, the tail
+    (-inf, -1, -1)."""
+    N = logits.shape[0]
+    G, K = N // W, 2 * W
+    x = logits[:, :vocab].float()
+    if mask is not None:
+        ids = torch.arange(vocab)
+        bits = (mask.reshape(-1, mask.shape[-1])[:, ids // 32] >> (ids % 32)) & 1
+        x = x.masked_fill(bits.expand(N, -1) == 0, float("-inf"))
+    m = torch.nan_to_num(x, nan=float("-inf")).amax(dim=-1, keepdim=True)
+    lse = m + torch.log(torch.exp(x - m).sum(dim=-1, keepdim=True))
+    s = cum[:N].float()[:, None] + (x - lse)
+    s = torch.where(torch.isfinite(s), s, torch.full((), float("-inf"))).reshape(G, W * vocab)
+    # (a stable descending sort: equal scores keep the ascending flat index b * vocab + v)
+    val, idx = torch.sort(s, dim=-1, descending=True, stable=True)
+    val, idx = val[:, :K], idx[:, :K]
+    if val.shape[1] < K:
+        pad = K - val.shape[1]
+        val = torch.cat([val, torch.full((G, pad), float("-inf"))], dim=1)
+        idx = torch.cat([idx, torch.zeros(G, pad, dtype=idx.dtype)], dim=1)
+    none = val == float("-inf")
+    cand_score[:G, :K] = val
+    cand_beam[:G, :K] = torch.where(none, -1, idx // vocab).to(cand_beam.dtype)
+    cand_tok[:G, :K] = torch.where(none, -1, idx % vocab).to(cand_tok.dtype)
+    return cand_score, cand_beam, cand_tok
+
+
+def kv_beam_gather(k_cache, v_cache, block_table, slots, parents, n_ctx, max_ctx):
+    """The beams' K/V follow their parents, in place (csrc/beam/beam.h): caches
+    [L, n_blocks, H, bs, hd]; for beam w of group g with parent p != w, blocks j <
+    ceil(min(n_ctx[g], max_ctx) / bs) of slot slots[g][w] take the old content of slot slots[g][p]'s."""
+    bs = k_cache.shape[3]
+    n_blocks = k_cache.shape[1]
+    sessions, bps = block_table.shape
+    G, W = slots.shape
+    for cache in (k_cache, v_cache):
+        for g in range(G):
+            ctx = min(max(int(n_ctx[g]), 0), bps * bs, int(max_ctx))
+            moves = []
+            for w in range(W):
+                p = int(parents[g, w])
+                sd = int(slots[g, w])
+                if p == w or not 0 <= p < W or not 0 <= sd < sessions:
+                    continue
+                ss = int(slots[g, p])
+                if not 0 <= ss < sessions:
+                    continue
+                for j in range((ctx + bs - 1) // bs):
+                    bd, bsrc = int(block_table[sd, j]), int(block_table[ss, j])
+                    if 1 <= bd < n_blocks and 1 <= bsrc < n_blocks:
+                        moves.append((bd, cache[:, bsrc].clone()))  # every source is read before any write
+            for bd, src in moves:
+                cache[:, bd] = src
+    return k_cache, v_cache

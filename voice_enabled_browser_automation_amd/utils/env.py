@@ -17,7 +17,7 @@ from __future__ import annotations
 import os
 from typing import Any, Optional
 
-from pydantic import BaseModel, Field
+from pydantic import BaseModel, Field, model_validator
 
 
 def _parse_env_file(path: str) -> dict:
@@ -118,6 +118,8 @@ class Settings(BaseModel):
     VWA_ASR_LANGUAGES: Optional[str] = Field(None, description="comma list of language codes that detection may report (unset: every language of the model)")
     VWA_ASR_TASK: str = Field("transcribe", description="Whisper task: transcribe | translate (to English)")
     VWA_ASR_NO_SPEECH: float = Field(0.0, description="no-speech gate: a window whose no-speech probability exceeds this yields an empty final and no partial (0: off; Whisper's customary threshold is 0.6)")
+    VWA_ASR_BEAM: int = Field(1, ge=1, le=8, description="beam width of the final recognition passes (1: greedy, the default; 2-8: beam search, csrc/beam -- a final pass then takes this many ASR session slots; partials and speculative passes stay greedy)")
+    VWA_ASR_ALTERNATIVES: int = Field(1, ge=1, le=8, description="ranked alternatives a final transcript event carries (Deepgram's alternatives; 1..VWA_ASR_BEAM)")
     VWA_CONTEXT_MAX_BYTES: int = Field(2048, description="per-session context cap sent to the brain")
     # ---- engine
     VWA_HIPGRAPH: bool = Field(True, description="replay decode steps from captured hipGraphs")
@@ -158,6 +160,13 @@ class Settings(BaseModel):
     VWA_FORCE_BUILD: bool = Field(False, description="__graft_entry__.build(): recompile every source")
     VWA_HIPCC_EXTRA: str = Field("", description="extra hipcc flags (experiments)")
 
+    @model_validator(mode="after")
+    def _alternatives_within_beam(self):
+        if self.VWA_ASR_ALTERNATIVES > self.VWA_ASR_BEAM:
+            raise ValueError(f"VWA_ASR_ALTERNATIVES={self.VWA_ASR_ALTERNATIVES} exceeds VWA_ASR_BEAM={self.VWA_ASR_BEAM}: "
+                             "a beam of W hypotheses has no more than W alternatives")
+        return self
+
     @classmethod
     def from_env(cls) -> "Settings":
         return cls(**{name: knob(name) for name in cls.model_fields})
@@ -192,6 +201,19 @@ def knob(name: str) -> Any:
         return _parse(name, raw)
     except ValueError as e:
         raise ValueError(f"{name}={raw!r}: {e}") from e
+
+
+def asr_beam_knobs(beam: Optional[int] = None, alternatives: Optional[int] = None) -> tuple:
+    """(beam width, alternatives) of the final recognition passes: the arguments, else VWA_ASR_BEAM /
+    VWA_ASR_ALTERNATIVES.  A width outside 1-8 or alternatives outside 1..width is an error (at
+    startup: the voice worker reads them when it builds its engine)."""
+    b = int(knob("VWA_ASR_BEAM") if beam is None else beam)
+    a = int(knob("VWA_ASR_ALTERNATIVES") if alternatives is None else alternatives)
+    if not 1 <= b <= 8:
+        raise ValueError(f"VWA_ASR_BEAM={b}: the beam width must be in 1..8")
+    if not 1 <= a <= b:
+        raise ValueError(f"VWA_ASR_ALTERNATIVES={a}: must be in 1..VWA_ASR_BEAM={b}")
+    return b, a
 
 
 def settings() -> Settings:

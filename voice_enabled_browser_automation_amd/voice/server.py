@@ -379,15 +379,18 @@ def asr_factory_from_env() -> Optional[Callable[[], Any]]:
         from ..runtime.weights import LazySafetensors
 
     model = WhisperModel(get_config(name), device=dev, weights=LazySafetensors(wpath) if wpath else None)
+    from ..utils.env import asr_beam_knobs
+
+    beam, n_alt = asr_beam_knobs()  # (a bad VWA_ASR_BEAM / VWA_ASR_ALTERNATIVES stops the worker here)
     eng = AsrEngine(model, load_tokenizer("whisper"),
-                    max_sessions=knob("VWA_MAX_SESSIONS"))
+                    max_sessions=max(knob("VWA_MAX_SESSIONS"), beam))  # a beam pass takes `beam` slots
     # VWA_ASR_TOKENS_PER_S: fixed-work transcripts for benchmarks on random-init weights
     tps = knob("VWA_ASR_TOKENS_PER_S") or None
     batcher = AsrBatcher(eng, tokens_per_s=tps)
     every = knob("VWA_PARTIAL_EVERY_S")
 
     def factory():
-        return StreamingAsrSession(batcher, model_name=name, partial_every_s=every)
+        return StreamingAsrSession(batcher, model_name=name, partial_every_s=every, beam=beam, alternatives=n_alt)
 
     factory.batcher = batcher
     return factory
