@@ -5,6 +5,7 @@ python tools/asr_timing.py [--asr whisper-large-v3] [--reps 10]
 python tools/asr_timing.py --words [--asr whisper-large-v3]   # the final pass without / with word timestamps
 python tools/asr_timing.py --language auto [--asr whisper-large-v3]   # the pass with a fixed / a detected language
 python tools/asr_timing.py --beam 5 [--asr whisper-large-v3]   # beam search against W greedy rows, per token step
+python tools/asr_timing.py --keyterms 50 [--batch-rows 8]   # the boosted step against plain rows
 
 decode_us_per_token = host time from the encoder's launch to the last token / tokens (includes the
 encoder and cross K/V projections still running after their launch); decode_gpu_us_per_token = the
@@ -44,6 +45,12 @@ def main():
     ap.add_argument("--beam", type=int, default=0,
                     help="time beam search of this width: per token step the select, the K/V gather and the whole "
                          "step, beside the same number of sessions decoded greedily as W independent rows")
+    ap.add_argument("--keyterms", type=int, default=0,
+                    help="time keyterm boosting with this many terms: the boosting launch alone (1 row and "
+                         "--batch-rows rows), and whole decode steps plain against boosted, for one session (the "
+                         "device loop; plain takes the persistent decoder where the model has one) and for "
+                         "--batch-rows batched sessions")
+    ap.add_argument("--batch-rows", type=int, default=8)
     ap.add_argument("--small-max-m", type=int, default=None,
                     help="A/B: rows up to which small weights take the one-tile kernel (16: the tiled GEMM above 16)")
     a = ap.parse_args()
@@ -139,6 +146,62 @@ def main():
                               greedy_rows_step_us=round(g, 1),
                               kernels_share_of_greedy_step=round((select_us + gather_us) / g, 4),
                               step_overhead_share=round(bm[0] / g - 1.0, 4))), flush=True)
+        return
+    if a.keyterms:  # decode_many(keyterms=): the boosting launch, and boosted steps against plain ones
+        from voice_enabled_browser_automation_amd.asr import keyterms as kt
+
+        R = a.batch_rows
+        eng = AsrEngine(m, load_tokenizer("whisper"), max_sessions=R)
+        audio = eng.pcm_to_audio(synth_speech(10.0, seed=100))
+        words = ["Grafana", "Browserbase", "pull request", "dashboard", "Kubernetes", "open settings", "checkout",
+                 "wireless earbuds", "sign in", "GitHub"]
+        ks = eng.compile_keyterms([f"{words[i % len(words)]} {i // len(words)}".strip() if i >= len(words)
+                                   else words[i] for i in range(a.keyterms)])
+
+        def timed(fn):
+            fn()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+            for e0, e1 in ev:
+                e0.record()
+                fn()
+                e1.record()
+            torch.cuda.synchronize()
+            return statistics.median(e0.elapsed_time(e1) for e0, e1 in ev) * 1e3
+
+        # the launch alone, on tables of its own (the set's, as kt.concat lays them out): every row at
+        # the root, moving by the first token of a term, in place
+        _, *tabs = kt.concat([ks])
+        tabs = tuple(torch.from_numpy(t).cuda() for t in tabs)
+        i32 = dict(dtype=torch.int32, device="cuda")
+        roots, state = torch.zeros(R, **i32), torch.zeros(R, **i32)
+        tok = torch.full((R,), ks.key[0][0][0], **i32)
+        launch = {}
+        for rows in (1, R):
+            x = torch.randn(rows, m.vocab_padded, device="cuda")
+            launch[rows] = timed(lambda: ops.boost_step(x, m.cfg.vocab_size, tabs, roots[:rows], state,
+                                                        state, tokens=tok[:rows]))
+        res = {}
+        for kind in ("plain_1", "boost_1", "plain_rows", "boost_rows") * 2:  # interleaved, reps each
+            n = 1 if kind.endswith("_1") else R
+            kw = dict(keyterms=[ks] * n) if kind.startswith("boost") else {}
+            for _ in range(2):
+                eng.decode_many([audio] * n, exact_tokens=a.tokens, **kw)
+            dgpu = []
+            for _ in range(a.reps):
+                eng.decode_many([audio] * n, exact_tokens=a.tokens, **kw)
+                dgpu.append(eng.last_stats.get("decode_gpu_ms") or 0.0)
+            res.setdefault(kind, []).append(statistics.median(dgpu) * 1e3 / a.tokens)
+        step = {k: min(v) for k, v in res.items()}
+        print(json.dumps(dict(tool="asr_timing", asr=a.asr, keyterms=a.keyterms, states=ks.n_states, edges=ks.n_edges,
+                              tokens=a.tokens, reps=a.reps, rows=R, boost_launch_us_1_row=round(launch[1], 1),
+                              boost_launch_us_rows=round(launch[R], 1),
+                              plain_step_us_1=round(step["plain_1"], 1), boost_step_us_1=round(step["boost_1"], 1),
+                              plain_step_us_rows=round(step["plain_rows"], 1),
+                              boost_step_us_rows=round(step["boost_rows"], 1),
+                              persistent_used_by_plain=bool(getattr(m, "_wdec", None)),
+                              step_overhead_share_1=round(step["boost_1"] / step["plain_1"] - 1.0, 4),
+                              step_overhead_share_rows=round(step["boost_rows"] / step["plain_rows"] - 1.0, 4))),
+              flush=True)
         return
     if a.language:  # the pass with the fixed default language and with --language (decode_many(languages=))
         eng = AsrEngine(m, load_tokenizer("whisper"), max_sessions=2)

@@ -159,6 +159,144 @@ class WhisperRunner:
         return out[:n]
 
 
+class BoostBuffers:
+    """The engine's keyterm boosting memory (built on the first boosted call): one int32 device
+    block of fixed size -- captured loop graphs address it -- and its pinned mirror,
+
+        roots [R] | state0 [R] | edge_off [CS + 1] | state_root [CS] | edge_tok | edge_next | edge_bias [CE each]
+
+    R = ops.BOOST_MAX_ROWS, CS / CE = ops.BOOST_CAP_STATES / BOOST_CAP_EDGES, plus two work state
+    rows.  Every launch covers all CS states and CE edges: states past those in use carry root -1 and
+    an empty list, so a stale state index becomes the row's root."""
+
+    def __init__(self, dev):
+        R, CS, CE = ops.BOOST_MAX_ROWS, ops.BOOST_CAP_STATES, ops.BOOST_CAP_EDGES
+        n = 2 * R + (CS + 1) + CS + 3 * CE
+        self.h = torch.zeros(n, dtype=torch.int32, pin_memory=dev.type == "cuda")
+        self.d = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.head = 2 * R
+        self.work = torch.zeros(2, R, dtype=torch.int32, device=dev)
+        self.key = None  # the automata the device tables hold (their keys, in table order; None: none)
+        self.bases: Dict[Tuple, int] = {}
+
+        def views(t):
+            o = 2 * R
+            parts = []
+            for m in (CS + 1, CS, CE, CE, CE):
+                parts.append(t[o : o + m])
+                o += m
+            off, root, tok, nxt, bias = parts
+            return t[:R], t[R : 2 * R], (off, tok, nxt, bias.view(torch.float32), root)
+
+        self.h_roots, self.h_state0, self.h_tables = views(self.h)
+        self.roots, self.state0, self.tables = views(self.d)
+
+
+class BoostRun:
+    """One decode_many call's keyterm boosting: which automaton each utterance has, where it sits in
+    the engine's tables, and the launches (ops.boost_step) in the three forms the decode paths use.
+    ``trace``: with AsrEngine.keep_boost_trace, one entry per launch."""
+
+    def __init__(self, bufs: BoostBuffers, sets: Sequence, vocab: int, trace: Optional[List[Dict]]):
+        from . import keyterms as kt
+
+        self.b = bufs
+        self.sets = list(sets)
+        self.vocab = vocab
+        self.trace = trace
+        distinct: Dict[Tuple, object] = {}
+        for ks in self.sets:
+            if ks is not None:
+                if not isinstance(ks, kt.KeytermSet):
+                    raise TypeError(f"keyterms: {type(ks).__name__} is not a compiled KeytermSet (asr/keyterms.py)")
+                distinct.setdefault(ks.key, ks)
+        S = sum(ks.n_states for ks in distinct.values())
+        E = sum(ks.n_edges for ks in distinct.values())
+        if S > ops.BOOST_CAP_STATES or E > ops.BOOST_CAP_EDGES:
+            raise RuntimeError(f"the call's {len(distinct)} keyterm automata hold {S} states / {E} edges: more than the "
+                               f"engine's tables ({ops.BOOST_CAP_STATES} / {ops.BOOST_CAP_EDGES})")
+        self.distinct = distinct
+        self.base: List[int] = []
+        self.cur = 0
+        self.n = 0
+        self.dirty = False
+
+    def load(self) -> None:
+        """Writes the call's tables into the pinned mirror when the device holds others (the copy
+        itself goes with the first ``stage``)."""
+        from . import keyterms as kt
+
+        keys = tuple(self.distinct)
+        b = self.b
+        if b.key != keys:
+            bases, off, tok, nxt, bias, root = kt.concat(list(self.distinct.values()))
+            h_off, h_tok, h_nxt, h_bias, h_root = b.h_tables
+            S, E = len(root), len(tok)
+            h_off.fill_(E)
+            h_off[: S + 1] = torch.from_numpy(off)
+            h_root.fill_(-1)
+            h_root[:S] = torch.from_numpy(root)
+            h_tok[:E] = torch.from_numpy(tok)
+            h_nxt[:E] = torch.from_numpy(nxt)
+            h_bias[:E] = torch.from_numpy(bias)
+            # (the device holds these only once stage() has queued the copy: until then it holds no
+            # set at all, so a call that fails in between leaves nothing a later call could trust)
+            b.key = None
+            b.bases = dict(zip(keys, bases))
+            self.dirty = True
+        self.keys = keys
+        self.base = [-1 if ks is None else b.bases[ks.key] for ks in self.sets]
+
+    def stage(self, utts: Sequence[int], hist: Sequence[Sequence[int]]) -> None:
+        """Row i is utterance utts[i] with text history hist[i]: its root and the state its
+        automaton is in after that history go to the device (with the tables, when they changed:
+        one copy either way)."""
+        b = self.b
+        self.n = n = len(utts)
+        assert 1 <= n <= ops.BOOST_MAX_ROWS
+        roots = [self.base[j] for j in utts]
+        b.h_roots.fill_(-1)
+        b.h_roots[:n] = torch.tensor(roots, dtype=torch.int32)
+        b.h_state0[:n] = torch.tensor([0 if r < 0 else r + self.sets[j].run(h) for r, j, h in zip(roots, utts, hist)],
+                                      dtype=torch.int32)
+        m = b.h.numel() if self.dirty else b.head
+        b.d[:m].copy_(b.h[:m], non_blocking=True)
+        if self.dirty:
+            b.key = self.keys
+        self.dirty = False
+        self.utts = list(utts)
+
+    def _launch(self, x: torch.Tensor, hist, state_in, state_out, **kw) -> None:
+        n = self.n
+        assert x.shape[0] == n
+        before = x.cpu().clone() if self.trace is not None else None
+        ops.boost_step(x, self.vocab, self.b.tables, self.b.roots[:n], state_in, state_out, **kw)
+        if self.trace is not None:
+            roots = [self.base[j] for j in self.utts]
+            self.trace.append(dict(utts=list(self.utts), history=[list(h) for h in hist], before=before,
+                                   after=x.cpu().clone(), sets=[self.sets[j] for j in self.utts],
+                                   state=[-1 if r < 0 else s - r for s, r in zip(state_out[:n].tolist(), roots)]))
+
+    def apply(self, x: torch.Tensor, hist) -> None:
+        """After ``stage``: the staged states' biases (no token to move on by)."""
+        self.cur = 0
+        self._launch(x, hist, self.b.state0, self.b.work[0])
+
+    def advance(self, x: torch.Tensor, tokens: torch.Tensor, hist) -> None:
+        """Every row moves on by its own last token, in place."""
+        w = self.b.work[self.cur]
+        self._launch(x, hist, w, w, tokens=tokens)
+
+    def follow(self, x: torch.Tensor, tokens: torch.Tensor, parents: torch.Tensor, W: int, hist) -> None:
+        """Beams: row r continues the state of its group's beam parents[r], then moves on by tokens[r]."""
+        self._launch(x, hist, self.b.work[self.cur], self.b.work[1 - self.cur], tokens=tokens, parents=parents, W=W)
+        self.cur = 1 - self.cur
+
+    def note(self, **kw) -> None:
+        if self.trace is not None and self.trace:
+            self.trace[-1].update(kw)
+
+
 class AsrEngine:
     """Whisper transcription with fixed-work decoding options for benchmarking."""
 
@@ -185,7 +323,9 @@ class AsrEngine:
         self.mask_text_eot = torch.from_numpy(self._pack(with_eot)).to(dev)[None]
         self.d_seed = torch.zeros(1, dtype=torch.int64, device=dev)
         self.d_step = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.d_tok = torch.zeros(1, dtype=torch.int32, device=dev)
+        # the sampler's tokens, one per row of the largest step: ONE buffer for the engine's life --
+        # captured loop graphs read it, and eager code hands them a token through it
+        self.d_tok = torch.zeros(max(max_sessions, max(BUCKETS)), dtype=torch.int32, device=dev)
         self.part_val = torch.zeros(64, dtype=torch.float32, device=dev)
         self.part_idx = torch.zeros(64, dtype=torch.int32, device=dev)
         self.language = str(knob("VWA_ASR_LANGUAGE") if language is None else language).strip().lower()
@@ -211,7 +351,7 @@ class AsrEngine:
         # device-resident single-session decode loop (graphs keyed by (slot, eot allowed))
         self.loop_out = torch.zeros(max(448, cfg.n_text_ctx), dtype=torch.int32, device=dev)
         self.loop_cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.loop_graphs: Dict[Tuple[int, bool, int], torch.cuda.CUDAGraph] = {}
+        self.loop_graphs: Dict[Tuple[int, bool, int, bool], torch.cuda.CUDAGraph] = {}
         self.device_loop = self.runner.use_graphs and ops.env_flag("VWA_ASR_DEVICE_LOOP")
         self.last_stats: Dict[str, float] = {}
         # decode_many(words=True): one entry per utterance of the last call (asr/words.py Alignment)
@@ -220,10 +360,31 @@ class AsrEngine:
         # with keep_beam_trace also one entry per step of the last call (_decode_beams)
         self.last_beams: List[List[Dict]] = []
         self.last_beam_trace: List[Dict] = []
+        # decode_many(keyterms=...): the keyterm tables' device memory (BoostBuffers), built by the first
+        # boosted call; with keep_boost_trace one entry per boosting launch of the last call (BoostRun)
+        self._boost_bufs: Optional[BoostBuffers] = None
+        self.last_boost_trace: List[Dict] = []
         self.free_slots = list(range(max_sessions - 1, -1, -1))
 
     keep_sot = False  # decode_many: always probe; keep host copies of the SOT logits and language probabilities
     keep_beam_trace = False  # decode_many with beams: keep host copies of every step's select inputs and outputs
+    # decode_many with keyterms: keep, per step, each live row's history, the logits before and after
+    # boosting, the automaton state and the chosen token (host copies); the call then steps from the
+    # host -- a single session does not take the device loop
+    keep_boost_trace = False
+
+    def compile_keyterms(self, terms, boost: Optional[float] = None):
+        """Text terms (strings, (text, boost) pairs) compiled for this engine's tokenizer: the
+        object ``decode_many(keyterms=[...])`` takes per utterance (asr/keyterms.py; None: no terms)."""
+        from . import keyterms as kt
+
+        return kt.compile_keyterms(terms, self.tok, self.model.cfg.eot, boost)
+
+    def _persistent_loop_ok(self, boost: Optional[BoostRun]) -> bool:
+        """The one routing decision for the persistent one-launch decoder (wdec_loop_step): its
+        argmax runs inside the kernel, before anything could bias the logits, so a boosted call
+        never takes it."""
+        return boost is None
 
     def _task_id(self, task: str) -> int:
         cfg = self.model.cfg
@@ -252,20 +413,29 @@ class AsrEngine:
     # decode_advance (sampled token becomes the next input, position / context / KV slot move on),
     # replayed back to back; the host reads the tokens once per chunk instead of once per token
     # (measured per token before: 5 metadata copies + a host round trip, ~80 us of GPU idle)
-    def _loop_step(self, slot: int, allow_eot: bool) -> None:
+    def _loop_step(self, slot: int, allow_eot: bool, boost: Optional[BoostRun] = None) -> None:
         r = self.runner
         b = r.b
         # whisper-large persistent decoder: embedding, layers, LM head, argmax and advance are ONE
         # launch (models/whisper.py wdec_loop_step)
-        if self.model.wdec_loop_step(
+        if self._persistent_loop_ok(boost) and self.model.wdec_loop_step(
                 b, self.mask_text_eot if allow_eot else self.mask_text, self.d_tok, self.d_step, self.loop_out,
                 self.loop_cnt, 1 + slot * r.bps):
             return
         logits = r._fwd(1)
-        self._advance(logits, slot, allow_eot)
+        self._advance(logits, slot, allow_eot, boost)
 
-    def _advance(self, logits: torch.Tensor, slot: int, allow_eot: bool) -> None:
+    def _advance(self, logits: torch.Tensor, slot: int, allow_eot: bool, boost: Optional[BoostRun] = None,
+                 first: bool = False) -> None:
+        """boost: the row's keyterm biases go onto the logits before the argmax reads them -- the
+        staged state's at the ``first`` step (after the prompt), afterwards the automaton moves on
+        by the token the previous step left in ``d_tok``, on the device (no host wait)."""
         b = self.runner.b
+        if boost is not None:
+            if first:
+                boost.apply(logits[:1], ())
+            else:
+                boost.advance(logits[:1], self.d_tok, ())
         ops.sample(logits[:1], mask=self.mask_text_eot if allow_eot else self.mask_text, temperature=None,
                    seed=self.d_seed, step=self.d_step, out_tokens=self.d_tok, part_val=self.part_val,
                    part_idx=self.part_idx)
@@ -274,8 +444,11 @@ class AsrEngine:
 
     LOOP_STEPS = 4  # decode steps per replayed loop graph (graph-to-graph launch gap ~10 us per replay)
 
-    def _loop_graph(self, slot: int, allow_eot: bool, steps: int = 1) -> "torch.cuda.CUDAGraph":
-        key = (slot, allow_eot, steps)
+    def _loop_graph(self, slot: int, allow_eot: bool, steps: int = 1,
+                    boost: Optional[BoostRun] = None) -> "torch.cuda.CUDAGraph":
+        # (a boosted loop is a graph of its own: it holds the boosting launch and not the persistent
+        # decoder; it addresses the engine's fixed boosting buffers, so it serves every boosted call)
+        key = (slot, allow_eot, steps, boost is not None)
         g = self.loop_graphs.get(key)
         if g is None:
             r = self.runner
@@ -288,21 +461,22 @@ class AsrEngine:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                self._loop_step(slot, allow_eot)
+                self._loop_step(slot, allow_eot, boost)
             torch.cuda.current_stream().wait_stream(s)
             g = torch.cuda.CUDAGraph()
             if r.pool is None:
                 r.pool = torch.cuda.graph_pool_handle()
             with torch.cuda.graph(g, pool=r.pool):
                 for _ in range(steps):  # identical steps: each reads what the previous advanced
-                    self._loop_step(slot, allow_eot)
+                    self._loop_step(slot, allow_eot, boost)
             self.loop_graphs[key] = g
         return g
 
     def _decode_device(self, slot: int, first_logits: torch.Tensor, n_max: int, exact: bool,
-                       P: Optional[int] = None) -> List[int]:
+                       P: Optional[int] = None, boost: Optional[BoostRun] = None) -> List[int]:
         """P: the session's prompt length (SOT sequence + any forced prefix) -- the first sampled
-        token sits at position P."""
+        token sits at position P.  boost: the session's staged keyterm run (row 0); the graphs'
+        warm-up step moves its work state, which the first advance sets again from the staged one."""
         cfg = self.model.cfg
         r = self.runner
         b = r.b
@@ -310,14 +484,14 @@ class AsrEngine:
         n_max = min(n_max, self.loop_out.numel(), r.bps * r.bs - P)
         if n_max <= 0:
             return []
-        g = self._loop_graph(slot, not exact)
+        g = self._loop_graph(slot, not exact, boost=boost)
         K = self.LOOP_STEPS
-        gk = self._loop_graph(slot, not exact, K) if K > 1 else None
+        gk = self._loop_graph(slot, not exact, K, boost=boost) if K > 1 else None
         # row 0 = this session at the last prompt position; the first advance moves it to P
         b.seq_ids[:1].fill_(slot)
         b.positions[:1].fill_(P - 1)
         self.loop_cnt.zero_()
-        self._advance(first_logits, slot, not exact)
+        self._advance(first_logits, slot, not exact, boost, first=True)
         out: List[int] = []
         done = 1
         chunk = n_max if exact else 8
@@ -375,7 +549,8 @@ class AsrEngine:
     def decode_many(self, audios: List[torch.Tensor], prefixes: Optional[Sequence[Sequence[int]]] = None, *,
                     max_tokens: int = 96, min_tokens: int = 0, exact_tokens: Optional[int] = None,
                     words: bool = False, languages: Optional[Sequence[Optional[str]]] = None,
-                    task: Optional[str] = None, beam_size: int = 1) -> List[List[int]]:
+                    task: Optional[str] = None, beam_size: int = 1,
+                    keyterms: Optional[Sequence] = None) -> List[List[int]]:
         """Token ids decoded for each utterance.  ``prefixes[i]``: text tokens forced after the
         SOT sequence (a streaming session's committed transcript -- asr/streaming.py local
         agreement): they are prefilled in the same ragged prompt step as the SOT tokens and only
@@ -400,7 +575,21 @@ class AsrEngine:
         hypotheses.  An utterance takes W session slots for the call -- the encoder and the cross K/V
         are computed once, into the first; the others' ``cross_table`` rows point at it and are
         restored when the call ends -- so B * W free slots (<= 64) are needed.  1: the greedy path,
-        and nothing of the beam library is loaded or launched."""
+        and nothing of the beam library is loaded or launched.
+
+        ``keyterms[i]``: utterance i's compiled keyterm set (``compile_keyterms``; asr/keyterms.py) or
+        None.  Every step's logits of a boosted row get ``bias(h, v)`` added (h: the forced prefix and
+        the tokens decoded so far -- a term may straddle the prefix boundary) by one launch
+        (ops.boost_step) before the argmax or the beam selection reads them, so the beams' scores and
+        ``last_beams`` log-probabilities are those of the biased distribution; ``_align`` keeps scoring
+        the model's own logits.  Identical sets share one automaton; the call's distinct automata
+        must fit the engine's tables (ops.BOOST_CAP_STATES / BOOST_CAP_EDGES) or the call raises
+        before anything is launched.  Host-to-device copies: one at the first step (the rows' roots and
+        initial states, with the tables when the device holds others), and -- batched rows and beams
+        only -- one more small one (roots and states, 512 bytes) at each step where a row or an
+        utterance has dropped out and the rows have moved up: the states are then staged again from
+        the histories the host holds, not compacted on the device.  A boosted call does not take the persistent one-launch decoder.
+        None, or a list of None: nothing of the boosting library is loaded, allocated or launched."""
         t0 = time.perf_counter()
         m = self.model
         B = len(audios)
@@ -414,6 +603,20 @@ class AsrEngine:
                                "free ASR session slots")
         prefixes = [list(p) for p in prefixes] if prefixes is not None else [[] for _ in range(B)]
         assert len(prefixes) == B
+        boost: Optional[BoostRun] = None
+        if keyterms is not None and any(k is not None for k in keyterms):
+            if len(keyterms) != B:
+                raise ValueError(f"keyterms: {len(keyterms)} entries for {B} utterances")
+            if B * W > ops.BOOST_MAX_ROWS:
+                raise RuntimeError(f"{B} boosted utterances of {W} rows exceed {ops.BOOST_MAX_ROWS} rows")
+            if self._boost_bufs is None:
+                self._boost_bufs = BoostBuffers(m.device)
+            if self.keep_boost_trace:
+                self.last_boost_trace = []
+            # (raises when the call's automata do not fit the tables: nothing is launched yet)
+            boost = BoostRun(self._boost_bufs, keyterms, m.cfg.vocab_size,
+                             self.last_boost_trace if self.keep_boost_trace else None)
+            boost.load()
         r = self.runner
         cap = r.bps * r.bs  # decoder positions per session
         cfg = m.cfg
@@ -425,6 +628,7 @@ class AsrEngine:
         heads = [[cfg.sot, self._lang_placeholder if a else language_token(cfg, l), task_id, cfg.no_timestamps]
                  for l, a in zip(langs, auto)]
         prompts = [h + p[: max(0, cap - len(h) - 1)] for h, p in zip(heads, prefixes)]
+        forced = [p[len(h):] for h, p in zip(heads, prompts)]  # the text prefix each decoder really gets
         probe = any(auto) or self.no_speech_threshold > 0.0 or self.keep_sot
         sot = None
         slots = [self.free_slots.pop() for _ in range(B)]
@@ -466,14 +670,35 @@ class AsrEngine:
             beam_ms = None
             if beam_slots is not None:
                 outs, beam_ms = self._decode_beams(beam_slots, logits, pos, limit, n_max, min_tokens,
-                                                   exact_tokens is not None)
+                                                   exact_tokens is not None, boost, forced)
                 live = []
-            elif B == 1 and self.device_loop and (exact_tokens is not None or min_tokens == 0) and n_max > 0:
-                outs[0] = self._decode_device(slots[0], logits, limit[0], exact_tokens is not None, P=pos[0])
+            elif (B == 1 and self.device_loop and (exact_tokens is not None or min_tokens == 0) and n_max > 0
+                  and not (boost is not None and self.keep_boost_trace)):  # (the trace steps from the host)
+                if boost is not None:
+                    boost.stage([0], [forced[0]])
+                    logits = logits.contiguous()
+                outs[0] = self._decode_device(slots[0], logits, limit[0], exact_tokens is not None, P=pos[0],
+                                              boost=boost)
                 live = []
+            staged: Optional[List[int]] = None  # the live rows the device's boosting states are those of
             for i in range(n_max if live else 0):
                 allow_eot = exact_tokens is None and i >= min_tokens
+                if boost is not None:
+                    # batched greedy rows: while the live set stands, every row's automaton moves on by
+                    # the token the sampler left on the device; when a row drops out the rows move up,
+                    # and the states are staged again from the histories the host has anyway
+                    logits = logits.contiguous()
+                    # (the histories are built only where they are read: to stage, or for the trace)
+                    hist = [forced[j] + outs[j] for j in live] if live != staged or boost.trace is not None else ()
+                    if live != staged:
+                        boost.stage(live, hist)
+                        boost.apply(logits, hist)
+                        staged = list(live)
+                    else:
+                        boost.advance(logits, self.d_tok, hist)
                 toks = self._sample_rows(logits, allow_eot)
+                if boost is not None:
+                    boost.note(tokens=list(toks), allow_eot=allow_eot)
                 nxt = []
                 for j, tok in zip(live, toks):
                     if tok == m.cfg.eot or tok < 0:
@@ -497,6 +722,8 @@ class AsrEngine:
                                    decode_gpu_ms=dec_gpu, total_ms=(t_end - t0) * 1e3,
                                    tokens=sum(len(o) for o in outs), batch=B,
                                    prefix_tokens=sum(len(p) - len(self.prompt) for p in prompts))
+            if boost is not None:
+                self.last_stats["boosted"] = sum(k is not None for k in keyterms)
             if beam_slots is not None:
                 self.last_stats["beam_size"] = W
                 if beam_ms is not None:
@@ -518,10 +745,11 @@ class AsrEngine:
                 self.free_slots.extend(reversed(slots + [s for bs_ in beam_slots for s in bs_[1:]]))
         return self.decode_many(audios, prefixes, max_tokens=max_tokens, min_tokens=min_tokens,
                                 exact_tokens=exact_tokens, words=words, languages=languages, task=task,
-                                beam_size=beam_size)
+                                beam_size=beam_size, keyterms=keyterms)
 
     def _decode_beams(self, beam_slots: List[List[int]], logits: torch.Tensor, pos: List[int], limit: List[int],
-                      n_max: int, min_tokens: int, exact: bool):
+                      n_max: int, min_tokens: int, exact: bool, boost: Optional[BoostRun] = None,
+                      forced: Optional[List[List[int]]] = None):
         """Beam search over every utterance of the call in one batch.  ``logits``: each utterance's
         last prompt row (the prompt is prefilled on beam 0's slot only); ``pos[i]``: utterance i's
         prompt length.  Per token step:
@@ -540,7 +768,13 @@ class AsrEngine:
         with ``keep_beam_trace``, ``last_beam_trace``: per step ``utts`` (the live utterances, in row
         order), ``logits`` [G W, vocab_padded] and ``cum`` [G, W] the select read, ``allow_eot`` (the
         mask: text ids with or without EOT), ``cand_score`` / ``cand_beam`` / ``cand_tok`` [G, 2 W],
-        and ``parents`` / ``tokens`` [G, W] chosen."""
+        and ``parents`` / ``tokens`` [G, W] chosen.
+
+        ``boost`` (``forced``: every utterance's text prefix): before each select the rows' keyterm
+        biases go onto ``x``.  The automaton states live on the device in two buffers and follow the
+        beams: row r starts from its parent's state and moves on by its token (the staging copy
+        carries the tokens too).  At the first step, and when an utterance has dropped out and the
+        rows have moved up, the states are staged from the beams' histories instead."""
         m = self.model
         cfg = m.cfg
         r = self.runner
@@ -556,7 +790,7 @@ class AsrEngine:
         if live != list(range(B)):
             x = x.view(B, W, -1)[live].reshape(len(live) * W, -1)
         res = torch.empty(3 * B * K, dtype=torch.float32, device=dev)  # score | beam | token, per step [3, G, K]
-        n_stage = B * (3 * W + 1)
+        n_stage = B * (3 * W + 1 + (W if boost is not None else 0))  # (boosted: the rows' tokens too)
         h_stage = torch.zeros(n_stage, dtype=torch.int32, pin_memory=cuda)  # slots | parents | cum bits | n_ctx
         d_stage = torch.zeros(n_stage, dtype=torch.int32, device=dev)
         timed: List[Tuple["torch.cuda.Event", "torch.cuda.Event"]] = []
@@ -568,29 +802,49 @@ class AsrEngine:
             e.record()
             return e
 
-        def stage(groups: List[int], parents: List[List[int]], n_ctx: List[int]):
+        def stage(groups: List[int], parents: List[List[int]], n_ctx: List[int],
+                  tokens: Optional[List[List[int]]] = None):
             G = len(groups)
-            hs = h_stage[: G * (3 * W + 1)]
+            n = G * (3 * W + 1)
+            hs = h_stage[:n]
             hs[: G * W] = torch.tensor([s for j in groups for s in beam_slots[j]], dtype=torch.int32)
             hs[G * W : 2 * G * W] = torch.tensor(parents, dtype=torch.int32).reshape(-1)
             hs[2 * G * W : 3 * G * W] = torch.tensor([c for j in groups for c in states[j].cum],
                                                      dtype=torch.float32).view(torch.int32)
             hs[3 * G * W :] = torch.tensor(n_ctx, dtype=torch.int32)
-            ds = d_stage[: G * (3 * W + 1)]
-            ds.copy_(hs, non_blocking=True)
+            tok_d = None
+            if boost is not None:  # the rows' tokens ride in the same copy
+                h_stage[n : n + G * W] = torch.tensor(tokens if tokens is not None else [[0] * W] * G,
+                                                      dtype=torch.int32).reshape(-1)
+                tok_d = d_stage[n : n + G * W]
+                n += G * W
+            d_stage[:n].copy_(h_stage[:n], non_blocking=True)
+            ds = d_stage
             return (ds[: G * W].view(G, W), ds[G * W : 2 * G * W].view(G, W),
-                    ds[2 * G * W : 3 * G * W].view(torch.float32), ds[3 * G * W :])
+                    ds[2 * G * W : 3 * G * W].view(torch.float32), ds[3 * G * W : G * (3 * W + 1)], tok_d)
 
         trace: List[Dict] = []
         self.last_beam_trace = trace
         t_a = mark()  # (the first select's bracket holds the first staging copy)
-        _, _, cum_d, _ = stage(live, [[0] * W for _ in live], [0] * len(live)) if live else (None,) * 4
+        _, _, cum_d, _, _ = stage(live, [[0] * W for _ in live], [0] * len(live)) if live else (None,) * 5
+        staged: Optional[List[int]] = None  # the live utterances the device's boosting states are those of
+        par_d = tok_d = None
         for i in range(n_max):
             if not live:
                 break
             G = len(live)
             allow_eot = not exact and i >= min_tokens
             cs, cb, ct = (res[k * G * K : (k + 1) * G * K].view(G, K) for k in range(3))
+            if boost is not None:
+                hist = ([forced[j] + states[j].tokens[w] for j in live for w in range(W)]
+                        if live != staged or boost.trace is not None else ())
+                if live != staged:
+                    boost.stage([j for j in live for _ in range(W)], hist)
+                    boost.apply(x, hist)
+                    staged = list(live)
+                else:
+                    boost.follow(x, tok_d, par_d.reshape(-1), W, hist)
+                boost.note(alive=[c != beam_rule.NEG_INF for j in live for c in states[j].cum], allow_eot=allow_eot)
             ops.beam_select(x, cum_d, self.mask_text_eot if allow_eot else self.mask_text, cfg.vocab_size, W,
                             cand_score=cs, cand_beam=cb.view(torch.int32), cand_tok=ct.view(torch.int32))
             h = res[: 3 * G * K].cpu()  # the one copy (it also waits for the step)
@@ -612,6 +866,9 @@ class AsrEngine:
                 if step is not None:
                     step["parents"].append(par)
                     step["tokens"].append(tok)
+                if boost is not None and boost.trace:
+                    boost.trace[-1].setdefault("parents", []).append(par)
+                    boost.trace[-1].setdefault("tokens", []).append(tok)
                 if not states[j].done:
                     nxt.append(j)
                     parents.append(par)
@@ -621,7 +878,7 @@ class AsrEngine:
                 break
             t_c = mark()
             n_ctx = [pos[j] + i for j in live]
-            slots_d, par_d, cum_d, ctx_d = stage(live, parents, n_ctx)
+            slots_d, par_d, cum_d, ctx_d, tok_d = stage(live, parents, n_ctx, tokens)
             ops.kv_beam_gather(b.k_cache, b.v_cache, b.block_table, slots_d, par_d, ctx_d, max_ctx=max(n_ctx))
             if cuda:
                 timed.append((t_c, mark()))  # (the forward that follows is not counted)
@@ -872,8 +1129,7 @@ class AsrEngine:
             return [self._sample(logits, allow_eot)]
         logits = logits.contiguous()
         mask = (self.mask_text_eot if allow_eot else self.mask_text).expand(n, -1).contiguous()
-        if self.d_tok.numel() < n:
-            self.d_tok = torch.zeros(n, dtype=torch.int32, device=self.d_tok.device)
+        assert n <= self.d_tok.numel()  # (a step has at most max(BUCKETS) rows; d_tok is never replaced)
         part_val = torch.empty(n * 64, dtype=torch.float32, device=logits.device)
         part_idx = torch.empty(n * 64, dtype=torch.int32, device=logits.device)
         ops.sample(logits, mask=mask, temperature=None, seed=self.d_seed, step=self.d_step, out_tokens=self.d_tok,

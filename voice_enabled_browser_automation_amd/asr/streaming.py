@@ -146,8 +146,14 @@ class StreamingAsrSession:
                  local_agreement: bool = True, spec_silence_s: Optional[float] = None,
                  noise_mult: Optional[float] = None, words: Optional[bool] = None, language: Optional[str] = None,
                  no_speech_threshold: Optional[float] = None, beam: Optional[int] = None,
-                 alternatives: Optional[int] = None):
+                 alternatives: Optional[int] = None, keyterms=None):
         from ..utils.env import asr_beam_knobs, knob
+
+        # keyterm boosting (asr/keyterms.py): the session's terms -- text terms or a compiled set --
+        # go with EVERY pass, partial, speculative and final (recognize(..., keyterms=...)), so the
+        # hypotheses local agreement compares are decoded under one bias.  None: no pass carries
+        # the keyword (recognizers with the old signature keep working)
+        self.keyterms = None
 
         # beam search on the final passes (VWA_ASR_BEAM; 1: greedy) and the ranked alternatives a
         # final event carries (VWA_ASR_ALTERNATIVES, 1..beam): the final pass and the speculative
@@ -207,7 +213,7 @@ class StreamingAsrSession:
         self.prev_tokens: List[int] = []  # previous interim hypothesis
         self.stats: Dict[str, float] = {"partials": 0, "finals": 0, "asr_ms": 0.0, "passes": 0,
                                         "committed_tokens": 0, "spec_started": 0, "spec_used": 0,
-                                        "spec_discarded": 0, "no_speech": 0}
+                                        "spec_discarded": 0, "no_speech": 0, "boosted_passes": 0}
         # on_speculative(text): called (from the recognizer's thread) when a speculative final pass
         # finishes while it still covers the utterance -- the voice server starts the brain on it
         # (voice/server.py: the brain's latency then overlaps the rest of the endpoint wait)
@@ -215,6 +221,8 @@ class StreamingAsrSession:
         # vad_events (Deepgram's live option of that name, off by default there too): push() also
         # returns {"type": "SpeechStarted"} when speech begins or resumes after a speculative final
         self.vad_events = False
+        if keyterms:
+            self.set_keyterms(keyterms)
 
     # ------------------------------------------------------------------ internals
     @property
@@ -235,7 +243,20 @@ class StreamingAsrSession:
             kw["beam"] = self.beam
         if self.language is not None:
             kw["language"] = self._lang_lock or self.language
+        if self.keyterms is not None:
+            kw["keyterms"] = self.keyterms
+            self.stats["boosted_passes"] += 1
         return kw
+
+    def set_keyterms(self, keyterms) -> None:
+        """Replace the session's keyterms (None or empty: none); in effect from the next pass.  A
+        recognizer that compiles terms (``compile_keyterms``: EngineRecognizer, AsrBatcher) does so
+        here, so a term it cannot take raises ValueError now and the old set stays."""
+        if not keyterms:
+            self.keyterms = None
+            return
+        comp = getattr(getattr(self, "rec", None), "compile_keyterms", None)
+        self.keyterms = comp(keyterms) if comp is not None else keyterms
 
     def _gated(self, hyp: Hypothesis) -> bool:
         p = getattr(hyp, "no_speech_prob", None)
@@ -442,7 +463,9 @@ def _hypothesis(eng, full: List[int], n_samples: int, al=None, sot: Optional[Dic
     own clock, and the transcript confidence (exp of the mean log-probability of its text tokens);
     with its ``last_sot`` entry the language and the no-speech probability; with its ``last_beams``
     entry (a beam pass: ranked {tokens, sum_logprob, avg_logprob}, ``prefix`` the forced tokens
-    before them) the alternatives after the first and the confidence exp(avg_logprob) of the best."""
+    before them) the alternatives after the first and the confidence exp(avg_logprob) of the best.
+    In a pass with keyterms the beams are scored on the biased logits, so these confidences are
+    those of the biased distribution; the words pass scores the model's own logits."""
     text = eng.tok.decode(full).strip()
     hyp = Hypothesis(full, text)
     if beams:
@@ -463,6 +486,16 @@ def _sot_of(eng, i: int) -> Optional[Dict]:
     return sots[i] if sots and i < len(sots) else None
 
 
+def _compile_keyterms(eng, keyterms):
+    """A pass's ``keyterms=`` as the engine takes it: a compiled set stays, text terms are compiled
+    with the engine's tokenizer (cached by content), None or empty is None."""
+    if not keyterms:
+        return None
+    from .keyterms import as_set
+
+    return as_set(keyterms, eng.tok, eng.model.cfg.eot)
+
+
 class EngineRecognizer:
     """Serial recognizer on an AsrEngine (one pass at a time, caller's thread)."""
 
@@ -473,10 +506,14 @@ class EngineRecognizer:
         self.max_tokens = max_tokens
         self.words = _words_knob(words)
 
+    def compile_keyterms(self, keyterms):
+        return _compile_keyterms(self.eng, keyterms)
+
     def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
-                  language: Optional[str] = None, beam: int = 1) -> Hypothesis:
+                  language: Optional[str] = None, beam: int = 1, keyterms=None) -> Hypothesis:
         """language: this pass's language code or "auto" (None: the engine's default); beam: the
-        pass's beam width (1: greedy) -- it then takes that many of the engine's session slots."""
+        pass's beam width (1: greedy) -- it then takes that many of the engine's session slots;
+        keyterms: this pass's keyterms, text terms or a compiled set (None: not boosted)."""
         prefix = list(prefix)[: self.eng.max_prefix()]  # the prefix the decoder actually forces
         words = bool(words) and self.words
         kw = {"words": True} if words else {}
@@ -484,6 +521,9 @@ class EngineRecognizer:
             kw["languages"] = [language]
         if beam > 1:
             kw["beam_size"] = int(beam)
+        ks = _compile_keyterms(self.eng, keyterms)
+        if ks is not None:
+            kw["keyterms"] = [ks]
         toks = self.eng.decode_many([self.eng.pcm_to_audio(pcm)], [prefix], max_tokens=self.max_tokens, **kw)[0]
         return _hypothesis(self.eng, prefix + toks, len(pcm), self.eng.last_alignments[0] if words else None,
                            _sot_of(self.eng, 0), self.eng.last_beams[0] if beam > 1 else None, prefix)
@@ -509,10 +549,14 @@ class AsrBatcher:
         # such a pass runs decode_many(words=True)
         self.words = _words_knob(words)
         self.max_batch = max_batch or len(asr_engine.free_slots)
+        from .. import ops
+
+        # what one call's distinct keyterm automata may hold together (the engine's tables)
+        self.cap_states, self.cap_edges = ops.BOOST_CAP_STATES, ops.BOOST_CAP_EDGES
         self._q: List[tuple] = []
         self._cv = threading.Condition()
         self._stop = False
-        self.stats = {"batches": 0, "passes": 0, "max_batch": 0, "gpu_ms": 0.0}
+        self.stats = {"batches": 0, "passes": 0, "max_batch": 0, "gpu_ms": 0.0, "boosted_passes": 0}
         # shared-GPU deployment: the brain reads this to keep its persistent chained decode launch
         # off the GPU while recognition runs (utils/busy_flag.py; launch.py sets the path)
         from ..utils.busy_flag import from_env
@@ -527,28 +571,39 @@ class AsrBatcher:
         self._thread = threading.Thread(target=self._loop, name="asr-batcher", daemon=True)
         self._thread.start()
 
+    def compile_keyterms(self, keyterms):
+        return _compile_keyterms(self.eng, keyterms)
+
     def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
-                  language: Optional[str] = None, beam: int = 1) -> Hypothesis:
-        return self.recognize_async(pcm, prefix, words=words, language=language, beam=beam).result()
+                  language: Optional[str] = None, beam: int = 1, keyterms=None) -> Hypothesis:
+        return self.recognize_async(pcm, prefix, words=words, language=language, beam=beam,
+                                    keyterms=keyterms).result()
 
     def recognize_async(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
-                        language: Optional[str] = None, beam: int = 1) -> Future:
+                        language: Optional[str] = None, beam: int = 1, keyterms=None) -> Future:
         """Queue a pass for the next GPU batch; the Future resolves to its Hypothesis.  language:
         this pass's code or "auto" (None: the engine's default); a batch may mix them.  beam: the
         pass's beam width (1: greedy).  A beam pass counts ``beam`` session slots; greedy passes and
         the beam passes of each width run as decode_many calls of their own, and a beam pass that
         does not fit a round's slots stays queued for the next (it is never failed for that).  A
-        width the engine's slots can never hold is refused here."""
+        width the engine's slots can never hold is refused here.  keyterms: this pass's keyterms
+        (text terms or a compiled set; None: not boosted); a batch may mix boosted and plain passes
+        and different sets.  A round whose distinct sets would not fit the engine's keyterm tables is
+        split -- the passes past the capacity stay queued; a set that alone exceeds it is refused here."""
         beam = int(beam)
         if beam < 1 or beam > min(8, self.max_batch):
             raise ValueError(f"beam = {beam} outside 1..{min(8, self.max_batch)} (the engine's session slots)")
+        ks = _compile_keyterms(self.eng, keyterms)
+        if ks is not None and (ks.n_states > self.cap_states or ks.n_edges > self.cap_edges):
+            raise ValueError(f"keyterms: {ks.n_states} states / {ks.n_edges} edges exceed the engine's tables "
+                             f"({self.cap_states} / {self.cap_edges})")
         fut: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("ASR batcher stopped")
             # (cut to what the decoder forces: the hypothesis is built on the prefix it really used)
             self._q.append((np.array(pcm, dtype=np.int16, copy=True), list(prefix)[: self.eng.max_prefix()], fut,
-                            bool(words) and self.words, language, beam))
+                            bool(words) and self.words, language, beam, ks))
             self._cv.notify()
         return fut
 
@@ -558,11 +613,20 @@ class AsrBatcher:
         the rest stays queued."""
         groups: Dict[int, List[tuple]] = {}
         used: Dict[int, int] = {}
+        sets: Dict[int, Dict] = {}  # per width: the distinct keyterm sets of its call, by key
         rest: List[tuple] = []
         for item in self._q:
-            w = item[5]
+            w, ks = item[5], item[6]
             cap = self.max_batch if w == 1 else min(self.max_batch, 64)
-            if used.get(w, 0) + w <= cap:
+            fits = used.get(w, 0) + w <= cap
+            if fits and ks is not None and ks.key not in sets.setdefault(w, {}):
+                # a set the call does not hold yet: the call's automata must still fit the tables
+                mine = list(sets[w].values()) + [ks]
+                fits = (sum(k.n_states for k in mine) <= self.cap_states
+                        and sum(k.n_edges for k in mine) <= self.cap_edges)
+                if fits:
+                    sets[w][ks.key] = ks
+            if fits:
                 groups.setdefault(w, []).append(item)
                 used[w] = used.get(w, 0) + w
             else:
@@ -611,6 +675,9 @@ class AsrBatcher:
                 kw["languages"] = [item[4] for item in batch]
             if beam > 1:
                 kw["beam_size"] = beam
+            if any(item[6] is not None for item in batch):
+                kw["keyterms"] = [item[6] for item in batch]
+                self.stats["boosted_passes"] += sum(item[6] is not None for item in batch)
             toks = self.eng.decode_many(audios, [item[1] for item in batch], **kw)
             als = self.eng.last_alignments if want else [None] * len(batch)
             beams = self.eng.last_beams if beam > 1 else [None] * len(batch)

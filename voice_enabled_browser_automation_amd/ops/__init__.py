@@ -1486,3 +1486,94 @@ def kv_beam_gather(k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: to
         ref.kv_beam_gather(k_cache, v_cache, block_table, slots, parents, n_ctx, max_ctx)
         return
     beam_ext().kv_beam_gather(k_cache, v_cache, block_table, slots.contiguous(), parents.contiguous(), n_ctx, max_ctx)
+
+
+# ----------------------------------------------------------------------------- keyterm boosting
+_BOOST = None
+_BOOST_ERR: Optional[BaseException] = None
+BOOST_MAX_ROWS = 64          # csrc/boost/boost.h kBoostMaxRows: rows per launch
+BOOST_MAX_STATES = 1 << 20   # ... kBoostMaxStates
+BOOST_MAX_EDGES = 1 << 24    # ... kBoostMaxEdges
+# what one decode_many call's distinct automata may hold together: the ASR engine keeps its tables
+# in device buffers of this fixed size (captured graphs address them), 0.85 MB in all (852,484 bytes).  A hundred
+# terms of six spellings and four tokens each are 2400 states
+BOOST_CAP_STATES = 8192
+BOOST_CAP_EDGES = 65536
+
+
+def boost_ext():
+    """Load the keyterm boosting library ``_vwa_boost.so`` (once). Raises if unavailable."""
+    global _BOOST, _BOOST_ERR
+    if _BOOST is not None:
+        return _BOOST
+    if _BOOST_ERR is not None:
+        raise RuntimeError(f"native gfx950 keyterm boosting library unavailable: {_BOOST_ERR}") from _BOOST_ERR
+    try:
+        from . import _vwa_boost as m  # type: ignore
+
+        _BOOST = m
+        return m
+    except BaseException as e:  # noqa: BLE001
+        _BOOST_ERR = e
+        raise RuntimeError(
+            "native gfx950 keyterm boosting library _vwa_boost.so failed to load; build it with "
+            "`python -m voice_enabled_browser_automation_amd.ops.build`"
+        ) from e
+
+
+def boost_step(logits: torch.Tensor, vocab: int, tables, roots: torch.Tensor, state_in: torch.Tensor,
+               state_out: torch.Tensor, *, tokens: Optional[torch.Tensor] = None,
+               parents: Optional[torch.Tensor] = None, W: int = 1) -> torch.Tensor:
+    """One keyterm boosting step, in place on f32 ``logits`` [>= rows, >= vocab] (asr/keyterms.py has
+    the semantics, csrc/boost/boost.h the per-row rule).  ``tables``: (edge_off int32 [S + 1],
+    edge_tok int32 [E], edge_next int32 [E], edge_bias f32 [E], state_root int32 [S]), the automata of
+    the call concatenated; ``roots`` int32 [rows <= 64]: each row's automaton root, -1: not boosted;
+    ``state_in`` / ``state_out`` int32 [>= rows]; ``tokens`` int32 [>= rows]: the token each row's
+    automaton moves on by before its biases are added (negative: the row is left alone; None: apply
+    only -- the first step after the prompt); ``parents`` int32 [>= rows] with group width ``W``: row
+    r starts from the state of row (r // W) * W + parents[r] (beams).  ``state_out`` may be
+    ``state_in`` itself only without parents.  Every boosted id below ``vocab`` gets one f32 add;
+    nothing else of the logits is read or written.  One launch on the GPU; host tensors take the
+    Python reference and never load the library."""
+    edge_off, edge_tok, edge_next, edge_bias, state_root = tables
+    i32, dev = torch.int32, logits.device
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise ValueError(f"boost_step: logits must be float32 [rows, >= vocab] with contiguous rows, not "
+                         f"{logits.dtype} {tuple(logits.shape)}")
+    if roots.dim() != 1 or roots.dtype != i32 or not 1 <= roots.numel() <= min(BOOST_MAX_ROWS, logits.shape[0]):
+        raise ValueError(f"boost_step: roots must be int32 [1..{min(BOOST_MAX_ROWS, logits.shape[0])}] (one per row of "
+                         f"the logits), not {roots.dtype} {tuple(roots.shape)}")
+    rows = roots.numel()
+    if not 1 <= vocab <= logits.shape[1]:
+        raise ValueError(f"boost_step: vocab = {vocab} outside [1, {logits.shape[1]}] (the logits' row length)")
+    S, E = state_root.numel(), edge_tok.numel()
+    if not 1 <= S <= BOOST_MAX_STATES or not 1 <= E <= BOOST_MAX_EDGES:
+        raise ValueError(f"boost_step: {S} states / {E} edges outside [1, {BOOST_MAX_STATES}] / [1, {BOOST_MAX_EDGES}]")
+    for name, t, dt, n, exact in (("edge_off", edge_off, i32, S + 1, True), ("edge_tok", edge_tok, i32, E, True),
+                                  ("edge_next", edge_next, i32, E, True), ("edge_bias", edge_bias, torch.float32, E, True),
+                                  ("state_root", state_root, i32, S, True), ("state_in", state_in, i32, rows, False),
+                                  ("state_out", state_out, i32, rows, False), ("tokens", tokens, i32, rows, False),
+                                  ("parents", parents, i32, rows, False)):
+        if t is None:
+            continue
+        if t.dim() != 1 or t.dtype != dt or not t.is_contiguous() or (t.numel() != n if exact else t.numel() < n):
+            raise ValueError(f"boost_step: {name} must be contiguous {dt} [{'' if exact else '>= '}{n}], not {t.dtype} "
+                             f"{tuple(t.shape)}")
+        if t.device != dev:
+            raise ValueError(f"boost_step: {name} is on {t.device}, the logits on {dev}")
+    if parents is not None:
+        W = int(W)
+        if not 1 <= W <= rows or rows % W:
+            raise ValueError(f"boost_step: {rows} rows are not groups of W = {W}")
+    a, b = state_in.data_ptr(), state_out.data_ptr()
+    if a < b + 4 * rows and b < a + 4 * rows and (parents is not None or a != b):
+        raise ValueError("boost_step: state_out may be state_in itself only without parents, and must not overlap it "
+                         "otherwise")
+    if not _gpu(logits):
+        ref.boost_step(logits, vocab, edge_off, edge_tok, edge_next, edge_bias, state_root, roots, state_in, state_out,
+                       tokens, parents, W)
+        return logits
+    # (a missing library raises: there is no other GPU path)
+    boost_ext().boost_step(logits, vocab, edge_off, edge_tok, edge_next, edge_bias, state_root, roots, state_in,
+                           state_out, tokens, parents, W)
+    return logits

@@ -9,6 +9,7 @@
 * ``_vwa_sot.so`` -- the start-of-transcript probe (``csrc/sot/*.hip`` + its own ``bindings.cpp``),
   likewise.
 * ``_vwa_beam.so`` -- the beam search steps (``csrc/beam/*.hip`` + its own ``bindings.cpp``), likewise.
+* ``_vwa_boost.so`` -- the keyterm boosting step (``csrc/boost/*.hip`` + its own ``bindings.cpp``), likewise.
 * ``_vwa_native.so`` -- the CPU runtime library (grammar engine, KV block manager): plain C++17
   with pybind11, built with g++.
 
@@ -36,6 +37,7 @@ NATIVE_SO = os.path.join(HERE, "_vwa_native.so")
 ALIGN_SO = os.path.join(HERE, "_vwa_align.so")
 SOT_SO = os.path.join(HERE, "_vwa_sot.so")
 BEAM_SO = os.path.join(HERE, "_vwa_beam.so")
+BOOST_SO = os.path.join(HERE, "_vwa_boost.so")
 
 
 def _torch_paths():
@@ -154,6 +156,11 @@ def build_beam(force: bool = False, jobs: int = 8) -> str:
     return _build_kernel_lib("beam", BEAM_SO, "_vwa_beam", force, jobs)
 
 
+def build_boost(force: bool = False, jobs: int = 8) -> str:
+    """Keyterm boosting library (automaton step + logit bias, one launch): csrc/boost -> _vwa_boost.so."""
+    return _build_kernel_lib("boost", BOOST_SO, "_vwa_boost", force, jobs)
+
+
 def build_native(force: bool = False) -> str:
     """CPU runtime library (grammar engine + block manager) -- g++ / pybind11."""
     srcs = sorted(glob.glob(os.path.join(CSRC, "runtime", "*.cpp")))
@@ -178,6 +185,7 @@ def build_all(force: bool = False) -> list[str]:
     out.append(build_align(force))
     out.append(build_sot(force))
     out.append(build_beam(force))
+    out.append(build_boost(force))
     return out
 
 

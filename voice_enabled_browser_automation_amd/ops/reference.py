@@ -500,3 +500,59 @@ def kv_beam_gather(k_cache, v_cache, block_table, slots, parents, n_ctx, max_ctx
             for bd, src in moves:
                 cache[:, bd] = src
     return k_cache, v_cache
+
+
+def boost_step(logits, vocab, edge_off, edge_tok, edge_next, edge_bias, state_root, roots, state_in, state_out,
+               tokens=None, parents=None, W=1):
+    """The keyterm boosting step on host tensors, rule by rule as csrc/boost/boost.h states it (one
+    f32 add per boosted id, so the result is bitwise what the kernel gives)."""
+    S, E = state_root.numel(), edge_tok.numel()
+    rows = roots.numel()
+    off, tok, nxt, root_of = edge_off.tolist(), edge_tok.tolist(), edge_next.tolist(), state_root.tolist()
+    old = state_in.tolist()  # (every source state is read before any is written)
+
+    def lst(s):
+        lo, hi = off[s], off[s + 1]
+        return range(lo, hi) if 0 <= lo <= hi <= E else range(0)
+
+    def find(s, v):
+        for e in lst(s):
+            if tok[e] == v:
+                return e
+        return -1
+
+    for r in range(rows):
+        root = int(roots[r])
+        if root < 0 or root >= S or root_of[root] != root:
+            state_out[r] = old[r]
+            continue
+        s = root
+        src = r
+        if parents is not None:
+            p = int(parents[r])
+            src = (r // W) * W + p if 0 <= p < W else -1
+        if 0 <= src < rows:
+            s = old[src]
+            if s < 0 or s >= S or root_of[s] != root:
+                s = root
+        if tokens is not None:
+            t = int(tokens[r])
+            if t < 0:
+                state_out[r] = s
+                continue
+            e = find(s, t)
+            if e < 0 and s != root:
+                e = find(root, t)
+            n = nxt[e] if e >= 0 else root
+            s = n if 0 <= n < S and root_of[n] == root else root
+        state_out[r] = s
+        mine = set()
+        for e in lst(s):
+            if 0 <= tok[e] < vocab:
+                logits[r, tok[e]] += edge_bias[e]
+            mine.add(tok[e])
+        if s != root:
+            for e in lst(root):
+                if 0 <= tok[e] < vocab and tok[e] not in mine:
+                    logits[r, tok[e]] += edge_bias[e]
+    return logits, state_out

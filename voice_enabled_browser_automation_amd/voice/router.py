@@ -161,7 +161,10 @@ def build_router(worker_urls: List[str], *, probe_s: Optional[float] = None,
             client.move.clear()
             moved = False
             try:
-                async with app["http"].ws_connect(worker.url + "/stream") as up:
+                # the client's query string goes to the worker as it came (keyterm=...: the session's
+                # keyterms, voice/server.py), on the first connection and after a failover alike
+                qs = req.query_string
+                async with app["http"].ws_connect(worker.url + "/stream" + (f"?{qs}" if qs else "")) as up:
                     if not first:
                         await ws.send_json({"type": "info", "payload": "asr_failover"})
                         m.inc("failovers")

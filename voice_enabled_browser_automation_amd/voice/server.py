@@ -18,7 +18,13 @@ Per connection:
     the connection's executor session id (``execution_result`` / ``execution_error``), risky
     ones produce ``confirmation_required``;
   * JSON control frames: ``{"type":"close"}``, ``{"type":"context_update","payload":{...}}``,
-    and ``{"type":"flush"}`` (end of utterance: finalise without waiting for silence).
+    ``{"type":"flush"}`` (end of utterance: finalise without waiting for silence) and
+    ``{"type":"keyterms","payload":{"terms":[...],"boost":x}}`` (replaces the session's keyterms);
+  * keyterm prompting as Deepgram's ``keyterm`` option: ``/stream?keyterm=Grafana&keyterm=pull+request:3``
+    -- repeated parameters, an optional ``:boost`` suffix in (0, 20] (a trailing ``:number`` is always
+    the boost: the term "10:30" is written ``10:30:2``), at most 100 terms -- names words
+    the recogniser should prefer (asr/keyterms.py); ``VWA_ASR_KEYTERMS`` gives every session default
+    terms.  Bad input is answered with a ``warn`` frame and the connection goes on.
 
 Races of the reference fixed here: brain calls of one connection are serialised
 by a per-connection lock (context updates apply in utterance order), and its executor calls run
@@ -44,6 +50,78 @@ from ..utils.metrics import Metrics
 from ..utils.env import knob
 
 VERSION = "0.1.0"
+
+
+MAX_KEYTERMS = 100      # Deepgram's limit on keyterms per request
+MAX_KEYTERM_BOOST = 20.0
+
+
+def parse_keyterm(raw: Any, default_boost: Optional[float] = None):
+    """One wire keyterm -> (text, boost): ``"pull request:3"``, ``"Grafana"`` (the default boost),
+    or {"term", "boost"}.  The boost is in (0, 20].  ValueError names what is wrong.
+
+    In the string form a trailing ``:number`` is ALWAYS the boost, so a term whose own text ends that
+    way ("10:30", "route:66") must name its boost after it -- ``"10:30:2"`` is the term "10:30" with
+    boost 2.  The {"term", "boost"} form takes ``term`` literally, colon and all."""
+    import math
+
+    if default_boost is None:
+        default_boost = knob("VWA_ASR_KEYTERM_BOOST")
+    boost: Any = None
+    literal = isinstance(raw, dict)
+    if literal:
+        raw, boost = raw.get("term", raw.get("text")), raw.get("boost")
+    if not isinstance(raw, str):
+        raise ValueError(f"keyterm {raw!r} is not a string")
+    text = raw.strip()
+    if not literal and ":" in text:
+        head, _, tail = text.rpartition(":")
+        try:
+            boost, text = float(tail), head.strip()
+        except ValueError:
+            pass  # (a colon inside the term itself)
+    if not text:
+        raise ValueError(f"keyterm {raw!r} is empty")
+    try:
+        b = float(default_boost if boost is None else boost)
+    except (TypeError, ValueError):
+        raise ValueError(f"keyterm {text!r}: boost {boost!r} is not a number") from None
+    if not math.isfinite(b) or not 0.0 < b <= MAX_KEYTERM_BOOST:
+        raise ValueError(f"keyterm {text!r}: boost {boost!r} outside (0, {MAX_KEYTERM_BOOST:g}]")
+    return text, b
+
+
+def parse_keyterms(raws, default_boost: Optional[float] = None):
+    """([(text, boost)], [warnings]): every usable term of the list, at most MAX_KEYTERMS."""
+    terms, warns = [], []
+    for raw in raws:
+        try:
+            t = parse_keyterm(raw, default_boost)
+        except ValueError as e:
+            warns.append(str(e))
+            continue
+        if len(terms) >= MAX_KEYTERMS:
+            warns.append(f"more than {MAX_KEYTERMS} keyterms: the rest are ignored")
+            break
+        if t not in terms:
+            terms.append(t)
+    return terms, warns
+
+
+def default_keyterms():
+    """The VWA_ASR_KEYTERMS terms (a comma list; a bad entry is an error at startup)."""
+    raw = knob("VWA_ASR_KEYTERMS") or ""
+    return [parse_keyterm(x) for x in raw.split(",") if x.strip()][:MAX_KEYTERMS]
+
+
+def _takes_keyterms(factory) -> bool:
+    import inspect
+
+    try:
+        ps = inspect.signature(factory).parameters
+    except (TypeError, ValueError):
+        return False
+    return "keyterms" in ps or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in ps.values())
 
 
 async def post_json_and_return(session: aiohttp.ClientSession, url: str, body: Any) -> Any:
@@ -130,10 +208,27 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
         # the recognizer's own state events {state: open|close|error, info}; a recognizer that
         # cannot be created -> error "deepgram_connect_failed" and the connection stays up
         # without transcription (as the reference, whose audio then goes nowhere)
+        # the session's keyterms: the query's, else the VWA_ASR_KEYTERMS defaults; what is wrong with
+        # them is reported once the recognizer frames are out
+        kt_warns: list = []
+        try:
+            keyterms, kt_warns = parse_keyterms(req.query.getall("keyterm", []))
+            keyterms = keyterms or default_keyterms()
+        except ValueError as e:
+            keyterms, kt_warns = [], [str(e)]
         asr = None
         if asr_factory is not None:
             try:
-                asr = asr_factory()
+                if keyterms and _takes_keyterms(asr_factory):
+                    try:
+                        asr = asr_factory(keyterms=keyterms)
+                    except ValueError as e:  # (a term the tokenizer cannot take: serve without)
+                        kt_warns.append(str(e))
+                        asr = asr_factory()
+                else:
+                    if keyterms:
+                        kt_warns.append("keyterms are not supported by this recognizer")
+                    asr = asr_factory()
             except Exception as e:  # noqa: BLE001
                 print(f"[voice] recognizer start failed: {e}", flush=True)
                 m.inc("asr_connect_failed")
@@ -146,6 +241,38 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
                     asr.on_speculative = lambda text: loop.call_soon_threadsafe(on_speculative_final, text)
         else:
             await send({"type": "warn", "payload": "no_api_key; running in passthrough"})
+        for w in kt_warns:
+            m.inc("keyterm_warnings")
+            await send({"type": "warn", "payload": f"keyterm: {w}"})
+        boosted_seen = [0]
+
+        def count_boosted():
+            """The session's recognition passes that carried keyterms -> the asr_boosted_passes counter."""
+            n = int((getattr(asr, "stats", None) or {}).get("boosted_passes", 0))
+            if n > boosted_seen[0]:
+                m.inc("asr_boosted_passes", n - boosted_seen[0])
+                boosted_seen[0] = n
+
+        async def set_keyterms(payload):
+            """The ``keyterms`` control frame: replaces the session's set from the next pass on."""
+            if not isinstance(payload, dict) or not isinstance(payload.get("terms"), list):
+                await send({"type": "warn", "payload": "keyterm: payload must be {terms: [...], boost?: x}"})
+                return
+            try:
+                dflt = payload.get("boost")
+                if dflt is not None:
+                    dflt = parse_keyterm("x", dflt)[1]
+                terms, warns = parse_keyterms(payload["terms"], dflt)
+                if asr is None or not hasattr(asr, "set_keyterms"):
+                    warns.append("keyterms are not supported by this recognizer")
+                else:
+                    asr.set_keyterms(terms)
+                    m.inc("keyterm_updates")
+            except ValueError as e:
+                warns = [str(e)]
+            for w in warns:
+                m.inc("keyterm_warnings")
+                await send({"type": "warn", "payload": f"keyterm: {w}"})
 
         async def asr_call(fn, *a):
             """One recognizer call on the worker pool; an engine failure is reported as the
@@ -304,6 +431,7 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
                     if asr is not None:
                         t_push = time.perf_counter()
                         events = await asr_call(asr.push, msg.data)
+                        count_boosted()
                         dt = time.perf_counter() - t_push
                         m.observe("asr_push_ms", dt * 1e3)
                         # a recognition pass ran: real-time factor = pass time over the seconds of
@@ -327,7 +455,10 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
                         st["ctx"] += 1
                     elif ctl.get("type") == "flush" and asr is not None:
                         events = await asr_call(asr.flush)
+                        count_boosted()
                         await handle_events(events)
+                    elif ctl.get("type") == "keyterms":
+                        await set_keyterms(ctl.get("payload"))
                 elif msg.type in (WSMsgType.ERROR, WSMsgType.CLOSE):
                     break
         finally:
@@ -389,8 +520,11 @@ def asr_factory_from_env() -> Optional[Callable[[], Any]]:
     batcher = AsrBatcher(eng, tokens_per_s=tps)
     every = knob("VWA_PARTIAL_EVERY_S")
 
-    def factory():
-        return StreamingAsrSession(batcher, model_name=name, partial_every_s=every, beam=beam, alternatives=n_alt)
+    default_keyterms()  # (a bad VWA_ASR_KEYTERMS stops the worker here)
+
+    def factory(keyterms=None):
+        return StreamingAsrSession(batcher, model_name=name, partial_every_s=every, beam=beam, alternatives=n_alt,
+                                   keyterms=keyterms)
 
     factory.batcher = batcher
     return factory
