@@ -6,6 +6,7 @@ python tools/asr_timing.py --words [--asr whisper-large-v3]   # the final pass w
 python tools/asr_timing.py --language auto [--asr whisper-large-v3]   # the pass with a fixed / a detected language
 python tools/asr_timing.py --beam 5 [--asr whisper-large-v3]   # beam search against W greedy rows, per token step
 python tools/asr_timing.py --keyterms 50 [--batch-rows 8]   # the boosted step against plain rows
+python tools/asr_timing.py --timestamps [--batch-rows 8]   # the timestamp rules step against plain rows, and the boundary pass
 
 decode_us_per_token = host time from the encoder's launch to the last token / tokens (includes the
 encoder and cross K/V projections still running after their launch); decode_gpu_us_per_token = the
@@ -50,6 +51,11 @@ def main():
                          "--batch-rows rows), and whole decode steps plain against boosted, for one session (the "
                          "device loop; plain takes the persistent decoder where the model has one) and for "
                          "--batch-rows batched sessions")
+    ap.add_argument("--timestamps", action="store_true",
+                    help="time timestamp decoding: the rules launch alone (1 row and --batch-rows rows, beside the "
+                         "boost launch of the same run), whole decode steps plain against timestamps for one session "
+                         "(the device loop; plain takes the persistent decoder where the model has one) and for "
+                         "--batch-rows batched sessions, and the boundary pass of a full 30 s window")
     ap.add_argument("--batch-rows", type=int, default=8)
     ap.add_argument("--small-max-m", type=int, default=None,
                     help="A/B: rows up to which small weights take the one-tile kernel (16: the tiled GEMM above 16)")
@@ -201,6 +207,89 @@ def main():
                               persistent_used_by_plain=bool(getattr(m, "_wdec", None)),
                               step_overhead_share_1=round(step["boost_1"] / step["plain_1"] - 1.0, 4),
                               step_overhead_share_rows=round(step["boost_rows"] / step["plain_rows"] - 1.0, 4))),
+              flush=True)
+        return
+    if a.timestamps:  # decode_many(timestamps=): the rules launch, and timestamp steps against plain ones
+        from voice_enabled_browser_automation_amd.asr import keyterms as kt
+        from voice_enabled_browser_automation_amd.asr.engine import TS_MAX_INITIAL
+
+        R = a.batch_rows
+        cfg = m.cfg
+        eng = AsrEngine(m, load_tokenizer("whisper"), max_sessions=R)
+        audio = eng.pcm_to_audio(synth_speech(10.0, seed=100))
+        window = eng.pcm_to_audio(synth_speech(30.0, seed=101))
+
+        def timed(fn):
+            fn()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+            for e0, e1 in ev:
+                e0.record()
+                fn()
+                e1.record()
+            torch.cuda.synchronize()
+            return statistics.median(e0.elapsed_time(e1) for e0, e1 in ev) * 1e3
+
+        # the launch alone, in the two states that cost most and least: text after text (the text
+        # maximum and the timestamps' log-sum-exp are both read, little is written) and text after a
+        # pair of timestamps (1501 columns written, the text read); beside it the boost launch of the
+        # same run (ten terms), which reads a few table entries and writes a few logits
+        eng._ts_setup()
+        i32 = dict(dtype=torch.int32, device="cuda")
+        tsb = cfg.no_timestamps + 1
+        enable = torch.ones(R, **i32)
+        ks = eng.compile_keyterms(["Grafana", "Browserbase", "pull request", "dashboard", "Kubernetes", "open settings",
+                                   "checkout", "wireless earbuds", "sign in", "GitHub"])
+        _, *tabs = kt.concat([ks])
+        tabs = tuple(torch.from_numpy(t).cuda() for t in tabs)
+        roots, bstate = torch.zeros(R, **i32), torch.zeros(R, **i32)
+        btok = torch.full((R,), ks.key[0][0][0], **i32)
+        launch = {}
+        for rows in (1, R):
+            x = torch.randn(rows, m.vocab_padded, device="cuda") * 3
+            for name, st in (("text", [2, 5, 6, 10]), ("pair", [2, tsb + 10, tsb + 10, 10])):
+                state = torch.tensor([st] * rows, **i32)
+                out = torch.empty_like(state)
+                launch[name, rows] = timed(lambda: ops.ts_rules_step(x, cfg.vocab_size, cfg.eot, tsb, TS_MAX_INITIAL,
+                                                                     eng.mask_ts_eot, enable[:rows], state, out))
+            launch["boost", rows] = timed(lambda: ops.boost_step(x, cfg.vocab_size, tabs, roots[:rows], bstate, bstate,
+                                                                 tokens=btok[:rows]))
+        res = {}
+        for kind in ("plain_1", "ts_1", "plain_rows", "ts_rows") * 2:  # interleaved, reps each
+            n = 1 if kind.endswith("_1") else R
+            kw = dict(timestamps=[True] * n) if kind.startswith("ts") else {}
+            for _ in range(2):
+                eng.decode_many([audio] * n, exact_tokens=a.tokens, **kw)
+            dgpu = []
+            for _ in range(a.reps):
+                eng.decode_many([audio] * n, exact_tokens=a.tokens, **kw)
+                dgpu.append(eng.last_stats.get("decode_gpu_ms") or 0.0)
+            res.setdefault(kind, []).append(statistics.median(dgpu) * 1e3 / a.tokens)
+        step = {k: min(v) for k, v in res.items()}
+        # the boundary pass of a full window: 30 s, half the decoder's context in tokens, one session
+        n_b = cfg.n_text_ctx // 2
+        for _ in range(2):
+            eng.decode_many([window], exact_tokens=n_b, timestamps=[True])
+        tot = []
+        for _ in range(max(3, a.reps // 2)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.decode_many([window], exact_tokens=n_b, timestamps=[True])
+            tot.append((time.perf_counter() - t0) * 1e3)
+        print(json.dumps(dict(tool="asr_timing", asr=a.asr, timestamps=True, tokens=a.tokens, reps=a.reps, rows=R,
+                              rules_launch_us_text_1_row=round(launch["text", 1], 1),
+                              rules_launch_us_pair_1_row=round(launch["pair", 1], 1),
+                              rules_launch_us_text_rows=round(launch["text", R], 1),
+                              rules_launch_us_pair_rows=round(launch["pair", R], 1),
+                              boost_launch_us_1_row=round(launch["boost", 1], 1),
+                              boost_launch_us_rows=round(launch["boost", R], 1),
+                              plain_step_us_1=round(step["plain_1"], 1), ts_step_us_1=round(step["ts_1"], 1),
+                              plain_step_us_rows=round(step["plain_rows"], 1), ts_step_us_rows=round(step["ts_rows"], 1),
+                              persistent_used_by_plain=bool(getattr(m, "_wdec", None)),
+                              ts_call_takes_persistent=eng._persistent_loop_ok(None, object()),
+                              step_overhead_share_1=round(step["ts_1"] / step["plain_1"] - 1.0, 4),
+                              step_overhead_share_rows=round(step["ts_rows"] / step["plain_rows"] - 1.0, 4),
+                              boundary_pass_tokens=n_b, boundary_pass_ms=round(statistics.median(tot), 2),
+                              boundary_pass_ms_min=round(min(tot), 2), boundary_pass_ms_max=round(max(tot), 2))),
               flush=True)
         return
     if a.language:  # the pass with the fixed default language and with --language (decode_many(languages=))

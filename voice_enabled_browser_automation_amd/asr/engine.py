@@ -19,6 +19,7 @@ from .. import ops
 from ..models.whisper import WhisperModel
 from ..tokenizer.languages import language_code, language_index, language_token
 from . import beam as beam_rule
+from .segments import segments
 from .words import Alignment, group_words
 
 BUCKETS = (1, 2, 4, 8, 16, 32, 64)
@@ -297,6 +298,82 @@ class BoostRun:
             self.trace[-1].update(kw)
 
 
+TS_MAX_INITIAL = 50  # the first timestamp of a window may be at most 1.0 s (Whisper's max_initial_timestamp)
+
+
+class TsBuffers:
+    """The engine's timestamp rules memory (built on the first timestamp call): one int32 device
+    block of fixed size -- captured loop graphs address it -- and its pinned mirror,
+
+        enable [R] | state0 [R, 4]
+
+    R = ops.TS_MAX_ROWS, plus the work states [R, 4] the launches step in place."""
+
+    def __init__(self, dev):
+        R = ops.TS_MAX_ROWS
+        self.h = torch.zeros(5 * R, dtype=torch.int32, pin_memory=dev.type == "cuda")
+        self.d = torch.zeros(5 * R, dtype=torch.int32, device=dev)
+        self.work = torch.zeros(R, 4, dtype=torch.int32, device=dev)
+        self.h_enable, self.h_state0 = self.h[:R], self.h[R:].view(R, 4)
+        self.enable, self.state0 = self.d[:R], self.d[R:].view(R, 4)
+
+
+def ts_state(hist: Sequence[int], ts_begin: int) -> List[int]:
+    """The rules' state (n, last, prev, last_ts) after the sampled tokens ``hist`` (csrc/tsrules/tsrules.h)."""
+    n = len(hist)
+    return [min(n, 2), hist[-1] if n >= 1 else -1, hist[-2] if n >= 2 else -1,
+            next((t - ts_begin for t in reversed(hist) if t >= ts_begin), -1)]
+
+
+class TsRun:
+    """One decode_many call's timestamp rules: which utterances decode with timestamps, and the
+    launches (ops.ts_rules_step) in the two forms the greedy paths use.  ``trace``: with
+    AsrEngine.keep_ts_trace, one entry per launch."""
+
+    def __init__(self, bufs: TsBuffers, flags: Sequence[bool], cfg, trace: Optional[List[Dict]]):
+        self.b = bufs
+        self.flags = [bool(f) for f in flags]
+        self.vocab, self.eot, self.ts_begin = cfg.vocab_size, cfg.eot, cfg.no_timestamps + 1
+        self.trace = trace
+        self.n = 0
+        self.utts: List[int] = []
+
+    def stage(self, utts: Sequence[int], hist: Sequence[Sequence[int]]) -> None:
+        """Row i is utterance utts[i] with the sampled tokens hist[i]: whether the rules hold for it
+        and the state they are in after that history go to the device (one copy)."""
+        b = self.b
+        self.n = n = len(utts)
+        assert 1 <= n <= ops.TS_MAX_ROWS
+        b.h_enable.zero_()
+        b.h_enable[:n] = torch.tensor([int(self.flags[j]) for j in utts], dtype=torch.int32)
+        b.h_state0[:n] = torch.tensor([ts_state(h, self.ts_begin) for h in hist], dtype=torch.int32)
+        b.d.copy_(b.h, non_blocking=True)
+        self.utts = list(utts)
+
+    def _launch(self, x: torch.Tensor, mask: torch.Tensor, hist, state_in, state_out, tokens=None) -> None:
+        n = self.n
+        assert x.shape[0] == n
+        before = x.cpu().clone() if self.trace is not None else None
+        ops.ts_rules_step(x, self.vocab, self.eot, self.ts_begin, TS_MAX_INITIAL, mask, self.b.enable[:n], state_in,
+                          state_out, tokens=tokens)
+        if self.trace is not None:
+            self.trace.append(dict(utts=list(self.utts), history=[list(h) for h in hist], before=before,
+                                   after=x.cpu().clone(), enable=[self.flags[j] for j in self.utts],
+                                   mask=mask.cpu().clone(), state=state_out[:n].tolist()))
+
+    def apply(self, x: torch.Tensor, mask: torch.Tensor, hist) -> None:
+        """After ``stage``: the rules at the staged states (no token to move on by)."""
+        self._launch(x, mask, hist, self.b.state0, self.b.work)
+
+    def advance(self, x: torch.Tensor, mask: torch.Tensor, tokens: torch.Tensor, hist) -> None:
+        """Every row moves on by its own last token, in place."""
+        self._launch(x, mask, hist, self.b.work, self.b.work, tokens=tokens)
+
+    def note(self, **kw) -> None:
+        if self.trace is not None and self.trace:
+            self.trace[-1].update(kw)
+
+
 class AsrEngine:
     """Whisper transcription with fixed-work decoding options for benchmarking."""
 
@@ -351,7 +428,7 @@ class AsrEngine:
         # device-resident single-session decode loop (graphs keyed by (slot, eot allowed))
         self.loop_out = torch.zeros(max(448, cfg.n_text_ctx), dtype=torch.int32, device=dev)
         self.loop_cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.loop_graphs: Dict[Tuple[int, bool, int, bool], torch.cuda.CUDAGraph] = {}
+        self.loop_graphs: Dict[Tuple[int, bool, int, bool, bool], torch.cuda.CUDAGraph] = {}
         self.device_loop = self.runner.use_graphs and ops.env_flag("VWA_ASR_DEVICE_LOOP")
         self.last_stats: Dict[str, float] = {}
         # decode_many(words=True): one entry per utterance of the last call (asr/words.py Alignment)
@@ -364,6 +441,15 @@ class AsrEngine:
         # boosted call; with keep_boost_trace one entry per boosting launch of the last call (BoostRun)
         self._boost_bufs: Optional[BoostBuffers] = None
         self.last_boost_trace: List[Dict] = []
+        # decode_many(timestamps=...): the rules' device memory (TsBuffers) and the two masks (text and
+        # timestamps, without / with EOT), built by the first timestamp call; per utterance of the last
+        # call its segments (asr/segments.py; None: decoded without timestamps); with keep_ts_trace one
+        # entry per rules launch of the last call (TsRun)
+        self._ts_bufs: Optional[TsBuffers] = None
+        self.mask_ts: Optional[torch.Tensor] = None
+        self.mask_ts_eot: Optional[torch.Tensor] = None
+        self.last_segments: List[Optional[List[Dict]]] = []
+        self.last_ts_trace: List[Dict] = []
         self.free_slots = list(range(max_sessions - 1, -1, -1))
 
     keep_sot = False  # decode_many: always probe; keep host copies of the SOT logits and language probabilities
@@ -372,6 +458,10 @@ class AsrEngine:
     # boosting, the automaton state and the chosen token (host copies); the call then steps from the
     # host -- a single session does not take the device loop
     keep_boost_trace = False
+    # decode_many with timestamps: keep, per step, each live row's sampled tokens, the logits before
+    # and after the rules, the rows' masks and the chosen tokens (host copies); the call then steps
+    # from the host, as with keep_boost_trace
+    keep_ts_trace = False
 
     def compile_keyterms(self, terms, boost: Optional[float] = None):
         """Text terms (strings, (text, boost) pairs) compiled for this engine's tokenizer: the
@@ -380,11 +470,29 @@ class AsrEngine:
 
         return kt.compile_keyterms(terms, self.tok, self.model.cfg.eot, boost)
 
-    def _persistent_loop_ok(self, boost: Optional[BoostRun]) -> bool:
+    def _persistent_loop_ok(self, boost: Optional[BoostRun], ts: Optional[TsRun] = None) -> bool:
         """The one routing decision for the persistent one-launch decoder (wdec_loop_step): its
-        argmax runs inside the kernel, before anything could bias the logits, so a boosted call
-        never takes it."""
-        return boost is None
+        argmax runs inside the kernel, before anything could bias or ban the logits, so a boosted
+        call and a timestamp call never take it."""
+        return boost is None and ts is None
+
+    def _ts_setup(self) -> None:
+        """The timestamp masks and buffers, on the first timestamp call."""
+        if self._ts_bufs is not None:
+            return
+        m = self.model
+        cfg = m.cfg
+        ids = np.arange(m.vocab_padded)
+        allowed = (ids < cfg.eot) | ((ids > cfg.no_timestamps) & (ids < cfg.vocab_size))
+        self.mask_ts = torch.from_numpy(self._pack(allowed)).to(m.device)[None]
+        allowed[cfg.eot] = True
+        self.mask_ts_eot = torch.from_numpy(self._pack(allowed)).to(m.device)[None]
+        self._ts_bufs = TsBuffers(m.device)
+
+    def _mask(self, allow_eot: bool, ts: bool = False) -> torch.Tensor:
+        if ts:
+            return self.mask_ts_eot if allow_eot else self.mask_ts
+        return self.mask_text_eot if allow_eot else self.mask_text
 
     def _task_id(self, task: str) -> int:
         cfg = self.model.cfg
@@ -403,8 +511,8 @@ class AsrEngine:
         t = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int16)).to(self.model.device, non_blocking=True)
         return ops.pcm16_to_f32(t, in_rate=rate)
 
-    def _sample(self, logits, allow_eot: bool) -> int:
-        ops.sample(logits, mask=self.mask_text_eot if allow_eot else self.mask_text, temperature=None,
+    def _sample(self, logits, allow_eot: bool, mask: Optional[torch.Tensor] = None) -> int:
+        ops.sample(logits, mask=self._mask(allow_eot) if mask is None else mask, temperature=None,
                    seed=self.d_seed, step=self.d_step, out_tokens=self.d_tok, part_val=self.part_val,
                    part_idx=self.part_idx)
         return int(self.d_tok[0].item())
@@ -413,30 +521,38 @@ class AsrEngine:
     # decode_advance (sampled token becomes the next input, position / context / KV slot move on),
     # replayed back to back; the host reads the tokens once per chunk instead of once per token
     # (measured per token before: 5 metadata copies + a host round trip, ~80 us of GPU idle)
-    def _loop_step(self, slot: int, allow_eot: bool, boost: Optional[BoostRun] = None) -> None:
+    def _loop_step(self, slot: int, allow_eot: bool, boost: Optional[BoostRun] = None,
+                   ts: Optional[TsRun] = None) -> None:
         r = self.runner
         b = r.b
         # whisper-large persistent decoder: embedding, layers, LM head, argmax and advance are ONE
         # launch (models/whisper.py wdec_loop_step)
-        if self._persistent_loop_ok(boost) and self.model.wdec_loop_step(
+        if self._persistent_loop_ok(boost, ts) and self.model.wdec_loop_step(
                 b, self.mask_text_eot if allow_eot else self.mask_text, self.d_tok, self.d_step, self.loop_out,
                 self.loop_cnt, 1 + slot * r.bps):
             return
         logits = r._fwd(1)
-        self._advance(logits, slot, allow_eot, boost)
+        self._advance(logits, slot, allow_eot, boost, ts=ts)
 
     def _advance(self, logits: torch.Tensor, slot: int, allow_eot: bool, boost: Optional[BoostRun] = None,
-                 first: bool = False) -> None:
+                 first: bool = False, ts: Optional[TsRun] = None) -> None:
         """boost: the row's keyterm biases go onto the logits before the argmax reads them -- the
         staged state's at the ``first`` step (after the prompt), afterwards the automaton moves on
-        by the token the previous step left in ``d_tok``, on the device (no host wait)."""
+        by the token the previous step left in ``d_tok``, on the device (no host wait).  ts: the
+        timestamp rules follow in the same manner, on the biased logits."""
         b = self.runner.b
         if boost is not None:
             if first:
                 boost.apply(logits[:1], ())
             else:
                 boost.advance(logits[:1], self.d_tok, ())
-        ops.sample(logits[:1], mask=self.mask_text_eot if allow_eot else self.mask_text, temperature=None,
+        mask = self._mask(allow_eot, ts is not None)
+        if ts is not None:
+            if first:
+                ts.apply(logits[:1], mask, ())
+            else:
+                ts.advance(logits[:1], mask, self.d_tok, ())
+        ops.sample(logits[:1], mask=mask, temperature=None,
                    seed=self.d_seed, step=self.d_step, out_tokens=self.d_tok, part_val=self.part_val,
                    part_idx=self.part_idx)
         ops.ext().decode_advance(b.tokens, b.positions, b.ctx_lens, b.slots, self.d_tok, self.loop_out,
@@ -444,11 +560,12 @@ class AsrEngine:
 
     LOOP_STEPS = 4  # decode steps per replayed loop graph (graph-to-graph launch gap ~10 us per replay)
 
-    def _loop_graph(self, slot: int, allow_eot: bool, steps: int = 1,
-                    boost: Optional[BoostRun] = None) -> "torch.cuda.CUDAGraph":
+    def _loop_graph(self, slot: int, allow_eot: bool, steps: int = 1, boost: Optional[BoostRun] = None,
+                    ts: Optional[TsRun] = None) -> "torch.cuda.CUDAGraph":
         # (a boosted loop is a graph of its own: it holds the boosting launch and not the persistent
-        # decoder; it addresses the engine's fixed boosting buffers, so it serves every boosted call)
-        key = (slot, allow_eot, steps, boost is not None)
+        # decoder; it addresses the engine's fixed boosting buffers, so it serves every boosted call.
+        # A timestamp loop likewise: the rules launch, the timestamp masks, the engine's fixed states)
+        key = (slot, allow_eot, steps, boost is not None, ts is not None)
         g = self.loop_graphs.get(key)
         if g is None:
             r = self.runner
@@ -461,19 +578,20 @@ class AsrEngine:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                self._loop_step(slot, allow_eot, boost)
+                self._loop_step(slot, allow_eot, boost, ts)
             torch.cuda.current_stream().wait_stream(s)
             g = torch.cuda.CUDAGraph()
             if r.pool is None:
                 r.pool = torch.cuda.graph_pool_handle()
             with torch.cuda.graph(g, pool=r.pool):
                 for _ in range(steps):  # identical steps: each reads what the previous advanced
-                    self._loop_step(slot, allow_eot, boost)
+                    self._loop_step(slot, allow_eot, boost, ts)
             self.loop_graphs[key] = g
         return g
 
     def _decode_device(self, slot: int, first_logits: torch.Tensor, n_max: int, exact: bool,
-                       P: Optional[int] = None, boost: Optional[BoostRun] = None) -> List[int]:
+                       P: Optional[int] = None, boost: Optional[BoostRun] = None,
+                       ts: Optional[TsRun] = None) -> List[int]:
         """P: the session's prompt length (SOT sequence + any forced prefix) -- the first sampled
         token sits at position P.  boost: the session's staged keyterm run (row 0); the graphs'
         warm-up step moves its work state, which the first advance sets again from the staged one."""
@@ -484,14 +602,14 @@ class AsrEngine:
         n_max = min(n_max, self.loop_out.numel(), r.bps * r.bs - P)
         if n_max <= 0:
             return []
-        g = self._loop_graph(slot, not exact, boost=boost)
+        g = self._loop_graph(slot, not exact, boost=boost, ts=ts)
         K = self.LOOP_STEPS
-        gk = self._loop_graph(slot, not exact, K, boost=boost) if K > 1 else None
+        gk = self._loop_graph(slot, not exact, K, boost=boost, ts=ts) if K > 1 else None
         # row 0 = this session at the last prompt position; the first advance moves it to P
         b.seq_ids[:1].fill_(slot)
         b.positions[:1].fill_(P - 1)
         self.loop_cnt.zero_()
-        self._advance(first_logits, slot, not exact, boost, first=True)
+        self._advance(first_logits, slot, not exact, boost, first=True, ts=ts)
         out: List[int] = []
         done = 1
         chunk = n_max if exact else 8
@@ -550,7 +668,8 @@ class AsrEngine:
                     max_tokens: int = 96, min_tokens: int = 0, exact_tokens: Optional[int] = None,
                     words: bool = False, languages: Optional[Sequence[Optional[str]]] = None,
                     task: Optional[str] = None, beam_size: int = 1,
-                    keyterms: Optional[Sequence] = None) -> List[List[int]]:
+                    keyterms: Optional[Sequence] = None,
+                    timestamps: Optional[Sequence[bool]] = None) -> List[List[int]]:
         """Token ids decoded for each utterance.  ``prefixes[i]``: text tokens forced after the
         SOT sequence (a streaming session's committed transcript -- asr/streaming.py local
         agreement): they are prefilled in the same ragged prompt step as the SOT tokens and only
@@ -589,7 +708,20 @@ class AsrEngine:
         only -- one more small one (roots and states, 512 bytes) at each step where a row or an
         utterance has dropped out and the rows have moved up: the states are then staged again from
         the histories the host holds, not compacted on the device.  A boosted call does not take the persistent one-launch decoder.
-        None, or a list of None: nothing of the boosting library is loaded, allocated or launched."""
+        None, or a list of None: nothing of the boosting library is loaded, allocated or launched.
+
+        ``timestamps[i]`` true: utterance i is decoded with timestamp tokens.  Its SOT sequence has no
+        ``<|notimestamps|>``, its masks allow text and timestamps, and one launch per step
+        (ops.ts_rules_step; csrc/tsrules/tsrules.h has Whisper's rules) bans what the rules forbid
+        after the tokens sampled so far -- after the boost, so the rules compare the biased logits, and
+        before the sampler.  Its tokens come back with the timestamp tokens among them and
+        ``self.last_segments[i]`` holds its segments (asr/segments.py; None for the other utterances).
+        Greedy only: with ``beam_size > 1``, ``words`` or a prefix on such an utterance the call raises
+        ValueError before anything is launched.  The rules' states advance on the device from the
+        sampler's tokens and are staged again from the host's histories when the rows move up; a
+        single session runs the captured device loop with the rules launch in its graph, and does
+        not take the persistent one-launch decoder.  None or all false: nothing of the rules library
+        is loaded, allocated or launched."""
         t0 = time.perf_counter()
         m = self.model
         B = len(audios)
@@ -603,6 +735,24 @@ class AsrEngine:
                                "free ASR session slots")
         prefixes = [list(p) for p in prefixes] if prefixes is not None else [[] for _ in range(B)]
         assert len(prefixes) == B
+        ts: Optional[TsRun] = None
+        ts_flags = [False] * B
+        if timestamps is not None and any(timestamps):
+            if len(timestamps) != B:
+                raise ValueError(f"timestamps: {len(timestamps)} entries for {B} utterances")
+            ts_flags = [bool(f) for f in timestamps]
+            if W > 1:
+                raise ValueError("timestamps: not with beam_size > 1 (the rules' state would have to follow the parents)")
+            if words:
+                raise ValueError("timestamps: not with words=True")
+            if any(f and p for f, p in zip(ts_flags, prefixes)):
+                raise ValueError("timestamps: an utterance decoded with timestamps takes no prefix")
+            if B > ops.TS_MAX_ROWS:
+                raise RuntimeError(f"{B} utterances with timestamps exceed {ops.TS_MAX_ROWS} rows")
+            self._ts_setup()
+            if self.keep_ts_trace:
+                self.last_ts_trace = []
+            ts = TsRun(self._ts_bufs, ts_flags, m.cfg, self.last_ts_trace if self.keep_ts_trace else None)
         boost: Optional[BoostRun] = None
         if keyterms is not None and any(k is not None for k in keyterms):
             if len(keyterms) != B:
@@ -627,6 +777,8 @@ class AsrEngine:
         task_id = self._task_id(self.task if task is None else str(task).strip().lower())
         heads = [[cfg.sot, self._lang_placeholder if a else language_token(cfg, l), task_id, cfg.no_timestamps]
                  for l, a in zip(langs, auto)]
+        if ts is not None:  # (an utterance decoded with timestamps: no <|notimestamps|>)
+            heads = [h[:3] if f else h for h, f in zip(heads, ts_flags)]
         prompts = [h + p[: max(0, cap - len(h) - 1)] for h, p in zip(heads, prefixes)]
         forced = [p[len(h):] for h, p in zip(heads, prompts)]  # the text prefix each decoder really gets
         probe = any(auto) or self.no_speech_threshold > 0.0 or self.keep_sot
@@ -673,14 +825,20 @@ class AsrEngine:
                                                    exact_tokens is not None, boost, forced)
                 live = []
             elif (B == 1 and self.device_loop and (exact_tokens is not None or min_tokens == 0) and n_max > 0
-                  and not (boost is not None and self.keep_boost_trace)):  # (the trace steps from the host)
+                  and not (boost is not None and self.keep_boost_trace)  # (the trace steps from the host)
+                  and not (ts is not None and self.keep_ts_trace)):
                 if boost is not None:
                     boost.stage([0], [forced[0]])
                     logits = logits.contiguous()
+                if ts is not None:
+                    ts.stage([0], [[]])
+                    logits = logits.contiguous()
                 outs[0] = self._decode_device(slots[0], logits, limit[0], exact_tokens is not None, P=pos[0],
-                                              boost=boost)
+                                              boost=boost, ts=ts)
                 live = []
             staged: Optional[List[int]] = None  # the live rows the device's boosting states are those of
+            ts_staged: Optional[List[int]] = None  # ... the device's timestamp states are those of
+            ts_masks: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # their masks, without / with EOT
             for i in range(n_max if live else 0):
                 allow_eot = exact_tokens is None and i >= min_tokens
                 if boost is not None:
@@ -696,9 +854,26 @@ class AsrEngine:
                         staged = list(live)
                     else:
                         boost.advance(logits, self.d_tok, hist)
-                toks = self._sample_rows(logits, allow_eot)
+                mask = None
+                if ts is not None:
+                    # the same scheme for the rules' states (the sampled tokens alone: such a row has no
+                    # prefix); every row brings its own mask, text rows the text mask
+                    logits = logits.contiguous()
+                    hist = [outs[j] for j in live] if live != ts_staged or ts.trace is not None else ()
+                    if live != ts_staged:
+                        ts_masks = tuple(torch.cat([self._mask(e, ts_flags[j]) for j in live]) for e in (False, True))
+                        mask = ts_masks[allow_eot]
+                        ts.stage(live, hist)
+                        ts.apply(logits, mask, hist)
+                        ts_staged = list(live)
+                    else:
+                        mask = ts_masks[allow_eot]
+                        ts.advance(logits, mask, self.d_tok, hist)
+                toks = self._sample_rows(logits, allow_eot, mask)
                 if boost is not None:
                     boost.note(tokens=list(toks), allow_eot=allow_eot)
+                if ts is not None:
+                    ts.note(tokens=list(toks), allow_eot=allow_eot)
                 nxt = []
                 for j, tok in zip(live, toks):
                     if tok == m.cfg.eot or tok < 0:
@@ -721,15 +896,19 @@ class AsrEngine:
             self.last_stats = dict(encode_ms=(t_enc - t0) * 1e3, decode_ms=(t_end - t_enc) * 1e3,
                                    decode_gpu_ms=dec_gpu, total_ms=(t_end - t0) * 1e3,
                                    tokens=sum(len(o) for o in outs), batch=B,
-                                   prefix_tokens=sum(len(p) - len(self.prompt) for p in prompts))
+                                   prefix_tokens=sum(len(f) for f in forced))
             if boost is not None:
                 self.last_stats["boosted"] = sum(k is not None for k in keyterms)
+            if ts is not None:
+                self.last_stats["timestamps"] = sum(ts_flags)
             if beam_slots is not None:
                 self.last_stats["beam_size"] = W
                 if beam_ms is not None:
                     self.last_stats["beam_ms"] = beam_ms()
             if not retry:
                 self.last_sot = self._read_sot(sot, langs, prompts)  # (fills in the detected language tokens)
+                self.last_segments = [segments(o, cfg.no_timestamps + 1, cfg.eot, self.tok) if f else None
+                                      for o, f in zip(outs, ts_flags)]
                 if words:
                     self.last_alignments = self._align(slots, audios, prompts, outs, exact_tokens is not None,
                                                        min_tokens)
@@ -745,7 +924,7 @@ class AsrEngine:
                 self.free_slots.extend(reversed(slots + [s for bs_ in beam_slots for s in bs_[1:]]))
         return self.decode_many(audios, prefixes, max_tokens=max_tokens, min_tokens=min_tokens,
                                 exact_tokens=exact_tokens, words=words, languages=languages, task=task,
-                                beam_size=beam_size, keyterms=keyterms)
+                                beam_size=beam_size, keyterms=keyterms, timestamps=timestamps)
 
     def _decode_beams(self, beam_slots: List[List[int]], logits: torch.Tensor, pos: List[int], limit: List[int],
                       n_max: int, min_tokens: int, exact: bool, boost: Optional[BoostRun] = None,
@@ -1123,12 +1302,14 @@ class AsrEngine:
         self.loop_graphs.clear()
         return True
 
-    def _sample_rows(self, logits: torch.Tensor, allow_eot: bool) -> List[int]:
+    def _sample_rows(self, logits: torch.Tensor, allow_eot: bool, mask: Optional[torch.Tensor] = None) -> List[int]:
+        """mask: the rows' own allow-bits [n, words] (a call with timestamp rows); None: the text mask."""
         n = logits.shape[0]
         if n == 1:
-            return [self._sample(logits, allow_eot)]
+            return [self._sample(logits, allow_eot, mask)]
         logits = logits.contiguous()
-        mask = (self.mask_text_eot if allow_eot else self.mask_text).expand(n, -1).contiguous()
+        if mask is None:
+            mask = self._mask(allow_eot).expand(n, -1).contiguous()
         assert n <= self.d_tok.numel()  # (a step has at most max(BUCKETS) rows; d_tok is never replaced)
         part_val = torch.empty(n * 64, dtype=torch.float32, device=logits.device)
         part_idx = torch.empty(n * 64, dtype=torch.int32, device=logits.device)

@@ -14,6 +14,11 @@ apps/web/src/App.tsx:279-288).  A session keeps the current utterance buffer and
 * on an endpoint (``endpoint_silence_s`` of silence after speech, ``VWA_ENDPOINT_MS``), on
   ``flush()`` (client end-of-utterance) or when the 30 s Whisper window is full, it emits a final
   result (``is_final: true, speech_final: true``) and starts a new utterance;
+* **long-form** (``VWA_ASR_LONGFORM``, off by default): a full window is not finalised whole.  One
+  boundary pass decodes it with timestamp tokens (asr/segments.py); the window is cut at the end
+  of the last segment that pass closes, the audio before the cut gets the normal final pass and
+  its final says ``speech_final: false`` (the speaker is still talking), and the audio after the
+  cut opens the next window of the same utterance -- no word is split by the cut;
 * **speculative final**: once the trailing silence reaches ``spec_silence_s``
   (``VWA_SPEC_FINAL_MS``, shorter than the endpoint) the final recognition pass is started in the
   background on the utterance so far; if the silence lasts to the endpoint its result IS the final
@@ -44,6 +49,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from .segments import cut_index, ts_time
 from .words import confidence as _confidence
 from .words import shift_words
 
@@ -51,21 +57,22 @@ from .words import shift_words
 def results_event(text: str, *, is_final: bool, start: float, duration: float, model: str,
                   confidence: float = 0.0, words: Optional[List[Dict]] = None, language: Optional[str] = None,
                   language_confidence: Optional[float] = None, no_speech_prob: Optional[float] = None,
-                  alternatives: Optional[List[Dict]] = None) -> Dict:
+                  alternatives: Optional[List[Dict]] = None, speech_final: Optional[bool] = None) -> Dict:
     """``words``: the alternative's Deepgram word list ({"word", "punctuated_word", "start", "end",
     "confidence"}, stream-clock seconds); None: the empty list.  ``language``: the detected (or
     set) language code -- Deepgram's ``channel.detected_language`` / ``language_confidence`` and
     the alternative's ``languages``.  ``no_speech_prob``: of a final the no-speech gate emptied
     (``metadata.no_speech_prob``).  ``alternatives``: the ranked hypotheses after the first
     ({"transcript", "confidence"}, from a beam pass) -- ``channel.alternatives[1:]`` in Deepgram's
-    shape, with no words.  Without them the event is unchanged."""
+    shape, with no words.  ``speech_final``: a final of a long utterance cut at a segment end says
+    False -- the speaker has not stopped (None: as ``is_final``).  Without them the event is unchanged."""
     ev = {
         "type": "Results",
         "channel_index": [0, 1],
         "duration": round(duration, 3),
         "start": round(start, 3),
         "is_final": is_final,
-        "speech_final": is_final,
+        "speech_final": is_final if speech_final is None else bool(speech_final),
         "channel": {"alternatives": [{"transcript": text, "confidence": confidence,
                                       "words": list(words) if words else []}]},
         "metadata": {"model_info": {"name": model}},
@@ -90,7 +97,9 @@ class Hypothesis:
     logits, the language the pass decoded under, its probability and the probability that the
     window holds no speech; from a beam pass, the ranked hypotheses after the first
     (``alternatives``: {"transcript", "confidence" = exp(avg_logprob)}) -- ``confidence`` is then
-    the best hypothesis' exp(avg_logprob) unless the words pass set it."""
+    the best hypothesis' exp(avg_logprob) unless the words pass set it; from a timestamp pass,
+    ``tokens`` holds the timestamp tokens too and ``segments`` the transcript's segments
+    (asr/segments.py: {start, end, tokens, text}, seconds from the window's start)."""
 
     tokens: List[int] = field(default_factory=list)
     text: str = ""
@@ -100,6 +109,7 @@ class Hypothesis:
     language_confidence: Optional[float] = None
     no_speech_prob: Optional[float] = None
     alternatives: List[Dict] = field(default_factory=list)
+    segments: List[Dict] = field(default_factory=list)
 
 
 class TextRecognizer:
@@ -146,8 +156,14 @@ class StreamingAsrSession:
                  local_agreement: bool = True, spec_silence_s: Optional[float] = None,
                  noise_mult: Optional[float] = None, words: Optional[bool] = None, language: Optional[str] = None,
                  no_speech_threshold: Optional[float] = None, beam: Optional[int] = None,
-                 alternatives: Optional[int] = None, keyterms=None):
+                 alternatives: Optional[int] = None, keyterms=None, longform: Optional[bool] = None):
         from ..utils.env import asr_beam_knobs, knob
+
+        # long utterances (VWA_ASR_LONGFORM, off by default): a full window is cut at the end of the
+        # last segment a timestamp pass closes, if that lies at or after VWA_ASR_LONGFORM_MIN_S (a
+        # policy default, not tuned on real speech: an earlier cut would refill the window at once)
+        self.longform = bool(knob("VWA_ASR_LONGFORM")) if longform is None else bool(longform)
+        self.longform_min = int(float(knob("VWA_ASR_LONGFORM_MIN_S")) * rate)
 
         # keyterm boosting (asr/keyterms.py): the session's terms -- text terms or a compiled set --
         # go with EVERY pass, partial, speculative and final (recognize(..., keyterms=...)), so the
@@ -213,7 +229,8 @@ class StreamingAsrSession:
         self.prev_tokens: List[int] = []  # previous interim hypothesis
         self.stats: Dict[str, float] = {"partials": 0, "finals": 0, "asr_ms": 0.0, "passes": 0,
                                         "committed_tokens": 0, "spec_started": 0, "spec_used": 0,
-                                        "spec_discarded": 0, "no_speech": 0, "boosted_passes": 0}
+                                        "spec_discarded": 0, "no_speech": 0, "boosted_passes": 0,
+                                        "longform_cuts": 0, "longform_fallbacks": 0}
         # on_speculative(text): called (from the recognizer's thread) when a speculative final pass
         # finishes while it still covers the utterance -- the voice server starts the brain on it
         # (voice/server.py: the brain's latency then overlaps the rest of the endpoint wait)
@@ -331,7 +348,52 @@ class StreamingAsrSession:
         except Exception:  # noqa: BLE001  (a listener failure must not break recognition)
             pass
 
-    def _final(self, use_spec: bool = True) -> List[Dict]:
+    def _cut_sample(self) -> Optional[int]:
+        """Long-form: the sample a full window is cut at, or None.  One boundary pass with
+        timestamps (the session's language and keyterms; no prefix, words or beam); the cut is the
+        end of the last segment it closes (asr/segments.py cut_index), when that lies at or after
+        the minimum and inside the window."""
+        t0 = time.perf_counter()
+        kw = {k: v for k, v in self._pass_kw(False).items() if k in ("language", "keyterms")}
+        hyp = self.rec.recognize(self.buf, (), timestamps=True, **kw)
+        self.stats["asr_ms"] += (time.perf_counter() - t0) * 1e3
+        self.stats["passes"] += 1
+        tsb = getattr(self.rec, "ts_begin", None)
+        if tsb is not None:
+            c = cut_index(hyp.tokens, tsb)
+            t = None if c is None else ts_time(hyp.tokens[c], tsb)
+        else:  # (a recognizer that reports segments only)
+            ends = [sg["end"] for sg in getattr(hyp, "segments", None) or [] if sg.get("end") is not None]
+            t = ends[-1] if ends else None
+        if t is None:
+            return None
+        cut = int(round(t * self.rate))
+        return cut if max(self.longform_min, 1) <= cut <= self._n else None
+
+    def _window_full(self) -> List[Dict]:
+        """The 30 s window filled while the speaker is still talking."""
+        cut = self._cut_sample() if self.longform and self.speech >= self.min_speech else None
+        if cut is None:
+            if self.longform:
+                self.stats["longform_fallbacks"] += 1
+            return self._final(use_spec=False)
+        n, speech, silence, lock = self._n, self.speech, self.trailing_silence, self._lang_lock
+        tail = self._pcm[cut:n].copy()
+        # the normal final pass on the audio before the cut; the committed prefix was agreed on the
+        # whole window and may reach past the cut, so this pass forces none
+        self._n = cut
+        self.committed = []
+        out = self._final(use_spec=False, speech_final=False)  # (t_offset moves on by the cut; the rest is cleared)
+        self._pcm[: len(tail)] = tail
+        self._n = len(tail)
+        # the utterance stays open: the endpoint, a flush or the next full window ends it
+        self.speech = max(min(speech, len(tail)), self.min_speech)
+        self.trailing_silence = min(silence, len(tail))
+        self._lang_lock = lock
+        self.stats["longform_cuts"] += 1
+        return out
+
+    def _final(self, use_spec: bool = True, speech_final: Optional[bool] = None) -> List[Dict]:
         out: List[Dict] = []
         if self.speech >= self.min_speech and len(self.buf):
             hyp = None
@@ -361,6 +423,8 @@ class StreamingAsrSession:
                 alts = list(getattr(hyp, "alternatives", None) or [])[: self.n_alternatives - 1]
                 if alts:
                     kw["alternatives"] = alts
+            if speech_final is not None:
+                kw["speech_final"] = speech_final
             out.append(results_event(text, is_final=True, start=self.t_offset, duration=len(self.buf) / self.rate,
                                      model=self.model_name, **kw, **self._lang_kw(hyp)))
             self.stats["finals"] += 1
@@ -429,7 +493,7 @@ class StreamingAsrSession:
             if self.speech >= self.min_speech and self.trailing_silence >= self.endpoint:
                 events += self._final()
             elif len(self.buf) >= self.max_window:
-                events += self._final(use_spec=False)
+                events += self._window_full() if self.longform else self._final(use_spec=False)
             elif (self.spec_at and self._spec is None and self.speech >= self.min_speech
                   and self.trailing_silence >= self.spec_at):
                 self._start_spec()
@@ -480,6 +544,25 @@ def _hypothesis(eng, full: List[int], n_samples: int, al=None, sot: Optional[Dic
     return hyp
 
 
+def _ts_hypothesis(eng, toks: List[int], i: int) -> Hypothesis:
+    """The hypothesis of a timestamp pass: every decoded token (the timestamp tokens among them),
+    the text of the text tokens alone, and utterance i's segments of the engine's last call."""
+    eot = eng.model.cfg.eot
+    hyp = Hypothesis(list(toks), eng.tok.decode([t for t in toks if t < eot]).strip())
+    segs = getattr(eng, "last_segments", None)
+    hyp.segments = list(segs[i]) if segs and i < len(segs) and segs[i] else []
+    sot = _sot_of(eng, i)
+    if sot is not None:
+        hyp.language, hyp.language_confidence = sot.get("language"), sot.get("language_confidence")
+        hyp.no_speech_prob = sot.get("no_speech_prob")
+    return hyp
+
+
+def _ts_tokens(eng) -> int:
+    """Tokens a timestamp pass may decode: half the decoder's context (Whisper's own sample length)."""
+    return eng.model.cfg.n_text_ctx // 2
+
+
 def _sot_of(eng, i: int) -> Optional[Dict]:
     """Utterance i's start-of-transcript report of the engine's last call (engines without: None)."""
     sots = getattr(eng, "last_sot", None)
@@ -506,24 +589,39 @@ class EngineRecognizer:
         self.max_tokens = max_tokens
         self.words = _words_knob(words)
 
+    @property
+    def ts_begin(self) -> int:
+        """The id of ``<|0.00|>``: what a session reads a timestamp pass's tokens with."""
+        return self.eng.model.cfg.no_timestamps + 1
+
     def compile_keyterms(self, keyterms):
         return _compile_keyterms(self.eng, keyterms)
 
     def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
-                  language: Optional[str] = None, beam: int = 1, keyterms=None) -> Hypothesis:
+                  language: Optional[str] = None, beam: int = 1, keyterms=None,
+                  timestamps: bool = False) -> Hypothesis:
         """language: this pass's language code or "auto" (None: the engine's default); beam: the
         pass's beam width (1: greedy) -- it then takes that many of the engine's session slots;
-        keyterms: this pass's keyterms, text terms or a compiled set (None: not boosted)."""
-        prefix = list(prefix)[: self.eng.max_prefix()]  # the prefix the decoder actually forces
-        words = bool(words) and self.words
-        kw = {"words": True} if words else {}
+        keyterms: this pass's keyterms, text terms or a compiled set (None: not boosted);
+        timestamps: decode with timestamp tokens, up to half the decoder's context whatever
+        ``max_tokens`` is -- such a pass carries no prefix, words or beam, and its hypothesis the
+        segments."""
+        kw: Dict[str, Any] = {}
         if language is not None:
             kw["languages"] = [language]
-        if beam > 1:
-            kw["beam_size"] = int(beam)
         ks = _compile_keyterms(self.eng, keyterms)
         if ks is not None:
             kw["keyterms"] = [ks]
+        if timestamps:
+            toks = self.eng.decode_many([self.eng.pcm_to_audio(pcm)], max_tokens=_ts_tokens(self.eng),
+                                        timestamps=[True], **kw)[0]
+            return _ts_hypothesis(self.eng, toks, 0)
+        prefix = list(prefix)[: self.eng.max_prefix()]  # the prefix the decoder actually forces
+        words = bool(words) and self.words
+        if words:
+            kw["words"] = True
+        if beam > 1:
+            kw["beam_size"] = int(beam)
         toks = self.eng.decode_many([self.eng.pcm_to_audio(pcm)], [prefix], max_tokens=self.max_tokens, **kw)[0]
         return _hypothesis(self.eng, prefix + toks, len(pcm), self.eng.last_alignments[0] if words else None,
                            _sot_of(self.eng, 0), self.eng.last_beams[0] if beam > 1 else None, prefix)
@@ -571,16 +669,23 @@ class AsrBatcher:
         self._thread = threading.Thread(target=self._loop, name="asr-batcher", daemon=True)
         self._thread.start()
 
+    @property
+    def ts_begin(self) -> int:
+        """The id of ``<|0.00|>``: what a session reads a timestamp pass's tokens with."""
+        return self.eng.model.cfg.no_timestamps + 1
+
     def compile_keyterms(self, keyterms):
         return _compile_keyterms(self.eng, keyterms)
 
     def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
-                  language: Optional[str] = None, beam: int = 1, keyterms=None) -> Hypothesis:
+                  language: Optional[str] = None, beam: int = 1, keyterms=None,
+                  timestamps: bool = False) -> Hypothesis:
         return self.recognize_async(pcm, prefix, words=words, language=language, beam=beam,
-                                    keyterms=keyterms).result()
+                                    keyterms=keyterms, timestamps=timestamps).result()
 
     def recognize_async(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
-                        language: Optional[str] = None, beam: int = 1, keyterms=None) -> Future:
+                        language: Optional[str] = None, beam: int = 1, keyterms=None,
+                        timestamps: bool = False) -> Future:
         """Queue a pass for the next GPU batch; the Future resolves to its Hypothesis.  language:
         this pass's code or "auto" (None: the engine's default); a batch may mix them.  beam: the
         pass's beam width (1: greedy).  A beam pass counts ``beam`` session slots; greedy passes and
@@ -589,8 +694,13 @@ class AsrBatcher:
         width the engine's slots can never hold is refused here.  keyterms: this pass's keyterms
         (text terms or a compiled set; None: not boosted); a batch may mix boosted and plain passes
         and different sets.  A round whose distinct sets would not fit the engine's keyterm tables is
-        split -- the passes past the capacity stay queued; a set that alone exceeds it is refused here."""
+        split -- the passes past the capacity stay queued; a set that alone exceeds it is refused here.
+        timestamps: decode with timestamp tokens (up to half the decoder's context; the hypothesis
+        carries the segments).  Such a pass is greedy and carries no prefix or words, and such
+        passes are batched among themselves: a decode_many call of their own."""
         beam = int(beam)
+        if timestamps:
+            prefix, words, beam = (), False, 1
         if beam < 1 or beam > min(8, self.max_batch):
             raise ValueError(f"beam = {beam} outside 1..{min(8, self.max_batch)} (the engine's session slots)")
         ks = _compile_keyterms(self.eng, keyterms)
@@ -603,32 +713,33 @@ class AsrBatcher:
                 raise RuntimeError("ASR batcher stopped")
             # (cut to what the decoder forces: the hypothesis is built on the prefix it really used)
             self._q.append((np.array(pcm, dtype=np.int16, copy=True), list(prefix)[: self.eng.max_prefix()], fut,
-                            bool(words) and self.words, language, beam, ks))
+                            bool(words) and self.words, language, beam, ks, bool(timestamps)))
             self._cv.notify()
         return fut
 
-    def _take(self) -> Dict[int, List[tuple]]:
-        """(under the lock) The queued passes of this round by beam width, in queue order: of each
-        width as many as the slots hold (a pass of width W counts W; a beam call holds <= 64 rows);
-        the rest stays queued."""
-        groups: Dict[int, List[tuple]] = {}
-        used: Dict[int, int] = {}
-        sets: Dict[int, Dict] = {}  # per width: the distinct keyterm sets of its call, by key
+    def _take(self) -> Dict[tuple, List[tuple]]:
+        """(under the lock) The queued passes of this round by (beam width, timestamps), in queue
+        order: of each kind as many as the slots hold (a pass of width W counts W; a beam call and a
+        timestamp call hold <= 64 rows); the rest stays queued."""
+        groups: Dict[tuple, List[tuple]] = {}
+        used: Dict[tuple, int] = {}
+        sets: Dict[tuple, Dict] = {}  # per kind: the distinct keyterm sets of its call, by key
         rest: List[tuple] = []
         for item in self._q:
             w, ks = item[5], item[6]
-            cap = self.max_batch if w == 1 else min(self.max_batch, 64)
-            fits = used.get(w, 0) + w <= cap
-            if fits and ks is not None and ks.key not in sets.setdefault(w, {}):
+            g = (w, item[7])
+            cap = self.max_batch if g == (1, False) else min(self.max_batch, 64)
+            fits = used.get(g, 0) + w <= cap
+            if fits and ks is not None and ks.key not in sets.setdefault(g, {}):
                 # a set the call does not hold yet: the call's automata must still fit the tables
-                mine = list(sets[w].values()) + [ks]
+                mine = list(sets[g].values()) + [ks]
                 fits = (sum(k.n_states for k in mine) <= self.cap_states
                         and sum(k.n_edges for k in mine) <= self.cap_edges)
                 if fits:
-                    sets[w][ks.key] = ks
+                    sets[g][ks.key] = ks
             if fits:
-                groups.setdefault(w, []).append(item)
-                used[w] = used.get(w, 0) + w
+                groups.setdefault(g, []).append(item)
+                used[g] = used.get(g, 0) + w
             else:
                 rest.append(item)
         self._q = rest
@@ -654,19 +765,22 @@ class AsrBatcher:
                 if self._stop and not self._q:
                     return
                 groups = self._take()
-            for width in sorted(groups):  # greedy passes first, then one call per beam width
-                self._run_batch(groups[width], width)
+            # greedy passes first, then the timestamp passes, then one call per beam width
+            for width, ts in sorted(groups):
+                self._run_batch(groups[(width, ts)], width, ts)
 
-    def _run_batch(self, batch: List[tuple], beam: int) -> None:
-        """One decode_many call: the round's greedy passes (beam 1) or its beam passes of one width."""
+    def _run_batch(self, batch: List[tuple], beam: int, timestamps: bool = False) -> None:
+        """One decode_many call: the round's greedy passes (beam 1), its timestamp passes, or its
+        beam passes of one width."""
         t0 = time.perf_counter()
         if self.busy is not None:
             self.busy.enter()
         try:
             audios = [self.eng.pcm_to_audio(item[0]) for item in batch]
-            kw = dict(max_tokens=self.max_tokens)
+            max_tokens = _ts_tokens(self.eng) if timestamps else self.max_tokens
+            kw = dict(max_tokens=max_tokens)
             if self.tokens_per_s:
-                kw = dict(exact_tokens=max(1, min(self.max_tokens, max(
+                kw = dict(exact_tokens=max(1, min(max_tokens, max(
                     int(round(len(item[0]) / 16000 * self.tokens_per_s)) - len(item[1]) for item in batch))))
             want = any(item[3] for item in batch)
             if want:
@@ -678,13 +792,18 @@ class AsrBatcher:
             if any(item[6] is not None for item in batch):
                 kw["keyterms"] = [item[6] for item in batch]
                 self.stats["boosted_passes"] += sum(item[6] is not None for item in batch)
-            toks = self.eng.decode_many(audios, [item[1] for item in batch], **kw)
-            als = self.eng.last_alignments if want else [None] * len(batch)
-            beams = self.eng.last_beams if beam > 1 else [None] * len(batch)
-            for i, (item, t, al) in enumerate(zip(batch, toks, als)):
-                p, pre, fut, w = item[:4]
-                fut.set_result(_hypothesis(self.eng, pre + t, len(p), al if w else None, _sot_of(self.eng, i),
-                                           beams[i], pre))
+            if timestamps:
+                toks = self.eng.decode_many(audios, timestamps=[True] * len(batch), **kw)
+                for i, (item, t) in enumerate(zip(batch, toks)):
+                    item[2].set_result(_ts_hypothesis(self.eng, t, i))
+            else:
+                toks = self.eng.decode_many(audios, [item[1] for item in batch], **kw)
+                als = self.eng.last_alignments if want else [None] * len(batch)
+                beams = self.eng.last_beams if beam > 1 else [None] * len(batch)
+                for i, (item, t, al) in enumerate(zip(batch, toks, als)):
+                    p, pre, fut, w = item[:4]
+                    fut.set_result(_hypothesis(self.eng, pre + t, len(p), al if w else None, _sot_of(self.eng, i),
+                                               beams[i], pre))
         except BaseException as e:  # noqa: BLE001  (fail this batch's passes, keep serving)
             for item in batch:
                 if not item[2].done():

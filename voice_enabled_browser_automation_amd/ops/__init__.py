@@ -1577,3 +1577,90 @@ def boost_step(logits: torch.Tensor, vocab: int, tables, roots: torch.Tensor, st
     boost_ext().boost_step(logits, vocab, edge_off, edge_tok, edge_next, edge_bias, state_root, roots, state_in,
                            state_out, tokens, parents, W)
     return logits
+
+
+# ----------------------------------------------------------------------------- timestamp rules
+_TSRULES = None
+_TSRULES_ERR: Optional[BaseException] = None
+TS_MAX_ROWS = 64          # csrc/tsrules/tsrules.h kTsMaxRows: rows per launch
+TS_MAX_VOCAB = 1 << 20    # ... kTsMaxVocab
+
+
+def ts_rules_ext():
+    """Load the timestamp rules library ``_vwa_tsrules.so`` (once). Raises if unavailable."""
+    global _TSRULES, _TSRULES_ERR
+    if _TSRULES is not None:
+        return _TSRULES
+    if _TSRULES_ERR is not None:
+        raise RuntimeError(f"native gfx950 timestamp rules library unavailable: {_TSRULES_ERR}") from _TSRULES_ERR
+    try:
+        from . import _vwa_tsrules as m  # type: ignore
+
+        _TSRULES = m
+        return m
+    except BaseException as e:  # noqa: BLE001
+        _TSRULES_ERR = e
+        raise RuntimeError(
+            "native gfx950 timestamp rules library _vwa_tsrules.so failed to load; build it with "
+            "`python -m voice_enabled_browser_automation_amd.ops.build`"
+        ) from e
+
+
+def ts_rules_step(logits: torch.Tensor, vocab: int, eot: int, ts_begin: int, max_initial: int, mask: torch.Tensor,
+                  enable: torch.Tensor, state_in: torch.Tensor, state_out: torch.Tensor, *,
+                  tokens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One step of Whisper's timestamp rules, in place on f32 ``logits`` [>= rows, >= vocab]
+    (csrc/tsrules/tsrules.h has the per-row rule).  ``ts_begin``: the id of ``<|0.00|>``, ``eot <
+    ts_begin < vocab``; ``max_initial``: the largest timestamp index the first token may take
+    (negative: no limit); ``mask``: the sampler's packed allow-bits, int32 [1 or >= rows, >=
+    ceil(vocab / 32)] (one row: shared); ``enable`` int32 [rows <= 64]: <= 0 leaves the row alone;
+    ``state_in`` / ``state_out`` int32 [>= rows, 4] = (n, last, prev, last_ts), ``state_out`` may be
+    ``state_in`` itself; ``tokens`` int32 [>= rows]: the token each row's state moves on by before
+    the rules are applied (outside [0, vocab): the row is left alone; None: apply only -- the first
+    step after the prompt).  Forbidden ids get -inf; nothing else of the logits is written.  One
+    launch on the GPU; host tensors take the Python reference and never load the library."""
+    i32, dev = torch.int32, logits.device
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise ValueError(f"ts_rules_step: logits must be float32 [rows, >= vocab] with contiguous rows, not "
+                         f"{logits.dtype} {tuple(logits.shape)}")
+    if enable.dim() != 1 or enable.dtype != i32 or not enable.is_contiguous() \
+            or not 1 <= enable.numel() <= min(TS_MAX_ROWS, logits.shape[0]):
+        raise ValueError(f"ts_rules_step: enable must be contiguous int32 [1..{min(TS_MAX_ROWS, logits.shape[0])}] (one "
+                         f"per row of the logits), not {enable.dtype} {tuple(enable.shape)}")
+    rows = enable.numel()
+    vocab, eot, ts_begin, max_initial = int(vocab), int(eot), int(ts_begin), int(max_initial)
+    if not 1 <= vocab <= min(logits.shape[1], TS_MAX_VOCAB):
+        raise ValueError(f"ts_rules_step: vocab = {vocab} outside [1, {min(logits.shape[1], TS_MAX_VOCAB)}] (the logits' "
+                         "row length)")
+    if not 0 <= eot < ts_begin:
+        raise ValueError(f"ts_rules_step: eot = {eot} outside [0, ts_begin = {ts_begin})")
+    if not ts_begin < vocab:
+        raise ValueError(f"ts_rules_step: ts_begin = {ts_begin} not below vocab = {vocab}")
+    if not -(1 << 31) <= max_initial < (1 << 31):
+        raise ValueError(f"ts_rules_step: max_initial = {max_initial} does not fit int32")
+    words = (vocab + 31) // 32
+    if mask.dim() != 2 or mask.dtype != i32 or mask.stride(1) != 1 or mask.shape[1] < words \
+            or not (mask.shape[0] == 1 or mask.shape[0] >= rows):
+        raise ValueError(f"ts_rules_step: mask must be int32 [1 or >= {rows}, >= {words}] with contiguous rows, not "
+                         f"{mask.dtype} {tuple(mask.shape)}")
+    for name, t in (("state_in", state_in), ("state_out", state_out)):
+        if t.dim() != 2 or t.dtype != i32 or not t.is_contiguous() or t.shape[1] != 4 or t.shape[0] < rows:
+            raise ValueError(f"ts_rules_step: {name} must be contiguous int32 [>= {rows}, 4], not {t.dtype} "
+                             f"{tuple(t.shape)}")
+    if tokens is not None and (tokens.dim() != 1 or tokens.dtype != i32 or not tokens.is_contiguous()
+                               or tokens.numel() < rows):
+        raise ValueError(f"ts_rules_step: tokens must be contiguous int32 [>= {rows}], not {tokens.dtype} "
+                         f"{tuple(tokens.shape)}")
+    for name, t in (("mask", mask), ("enable", enable), ("state_in", state_in), ("state_out", state_out),
+                    ("tokens", tokens)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"ts_rules_step: {name} is on {t.device}, the logits on {dev}")
+    a, b = state_in.data_ptr(), state_out.data_ptr()
+    if a != b and a < b + 16 * rows and b < a + 16 * rows:
+        raise ValueError("ts_rules_step: state_out must be state_in itself or not overlap it")
+    if not _gpu(logits):
+        ref.ts_rules_step(logits, vocab, eot, ts_begin, max_initial, mask, enable, state_in, state_out, tokens)
+        return logits
+    # (a missing library raises: there is no other GPU path)
+    ts_rules_ext().ts_rules_step(logits, vocab, eot, ts_begin, max_initial, mask, enable, state_in, state_out, tokens)
+    return logits

@@ -10,6 +10,7 @@
   likewise.
 * ``_vwa_beam.so`` -- the beam search steps (``csrc/beam/*.hip`` + its own ``bindings.cpp``), likewise.
 * ``_vwa_boost.so`` -- the keyterm boosting step (``csrc/boost/*.hip`` + its own ``bindings.cpp``), likewise.
+* ``_vwa_tsrules.so`` -- the timestamp rules step (``csrc/tsrules/*.hip`` + its own ``bindings.cpp``), likewise.
 * ``_vwa_native.so`` -- the CPU runtime library (grammar engine, KV block manager): plain C++17
   with pybind11, built with g++.
 
@@ -38,6 +39,7 @@ ALIGN_SO = os.path.join(HERE, "_vwa_align.so")
 SOT_SO = os.path.join(HERE, "_vwa_sot.so")
 BEAM_SO = os.path.join(HERE, "_vwa_beam.so")
 BOOST_SO = os.path.join(HERE, "_vwa_boost.so")
+TSRULES_SO = os.path.join(HERE, "_vwa_tsrules.so")
 
 
 def _torch_paths():
@@ -161,6 +163,11 @@ def build_boost(force: bool = False, jobs: int = 8) -> str:
     return _build_kernel_lib("boost", BOOST_SO, "_vwa_boost", force, jobs)
 
 
+def build_tsrules(force: bool = False, jobs: int = 8) -> str:
+    """Timestamp rules library (state step + logit bans, one launch): csrc/tsrules -> _vwa_tsrules.so."""
+    return _build_kernel_lib("tsrules", TSRULES_SO, "_vwa_tsrules", force, jobs)
+
+
 def build_native(force: bool = False) -> str:
     """CPU runtime library (grammar engine + block manager) -- g++ / pybind11."""
     srcs = sorted(glob.glob(os.path.join(CSRC, "runtime", "*.cpp")))
@@ -186,6 +193,7 @@ def build_all(force: bool = False) -> list[str]:
     out.append(build_sot(force))
     out.append(build_beam(force))
     out.append(build_boost(force))
+    out.append(build_tsrules(force))
     return out
 
 

@@ -556,3 +556,56 @@ def boost_step(logits, vocab, edge_off, edge_tok, edge_next, edge_bias, state_ro
                 if 0 <= tok[e] < vocab and tok[e] not in mine:
                     logits[r, tok[e]] += edge_bias[e]
     return logits, state_out
+
+
+def ts_rules_step(logits, vocab, eot, ts_begin, max_initial, mask, enable, state_in, state_out, tokens=None):
+    """The timestamp rules step on host tensors, rule by rule as csrc/tsrules/tsrules.h states it
+    (T in f64: the kernel's f32 T decides differently only where T and M all but tie)."""
+    rows = enable.numel()
+    n_ts = vocab - ts_begin
+    ninf = float("-inf")
+    old = state_in[:rows].tolist()  # (in place: every row's cells are read before they are written)
+    ids = torch.arange(vocab)
+    for r in range(rows):
+        t = None if tokens is None else int(tokens[r])
+        if int(enable[r]) <= 0 or (t is not None and not 0 <= t < vocab):
+            state_out[r] = torch.tensor(old[r], dtype=torch.int32)
+            continue
+        n, last, prev, last_ts = old[r]
+        if not 0 <= n <= 2 or not -1 <= last_ts < n_ts:
+            n, last, prev, last_ts = 0, -1, -1, -1
+        if t is not None:
+            prev, last, n = last, t, min(n + 1, 2)
+            if t >= ts_begin:
+                last_ts = t - ts_begin
+        state_out[r] = torch.tensor([n, last, prev, last_ts], dtype=torch.int32)
+        x = logits[r]
+        m = mask[r if mask.shape[0] > 1 else 0]
+        ok = ((m[ids >> 5] >> (ids & 31)) & 1).bool()  # allowed by the mask and not banned so far
+        banned = torch.zeros(vocab, dtype=torch.bool)
+
+        def ban(lo, hi):
+            banned[max(lo, 0) : max(min(hi, vocab), 0)] = True
+
+        ban(ts_begin - 1, ts_begin)
+        last_was = n >= 1 and last >= ts_begin
+        pen_was = n < 2 or prev >= ts_begin
+        if last_was and pen_was:
+            ban(ts_begin, vocab)
+        elif last_was:
+            ban(0, eot)
+        if last_ts >= 0:
+            ban(ts_begin, ts_begin + (last_ts if last_was and not pen_was else last_ts + 1))
+        if n == 0:
+            ban(0, ts_begin)
+            if max_initial >= 0:
+                ban(ts_begin + max_initial + 1, vocab)
+        live = ok & ~banned
+        xs = x[:vocab].double()
+        ts, tx = xs[ts_begin:][live[ts_begin:]], xs[:ts_begin][live[:ts_begin]]
+        T = float(torch.logsumexp(ts, 0)) if ts.numel() else ninf
+        M = float(tx.max()) if tx.numel() else ninf
+        if T > M:
+            ban(0, ts_begin)
+        x[:vocab][banned] = ninf
+    return logits, state_out

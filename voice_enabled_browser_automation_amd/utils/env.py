@@ -120,6 +120,8 @@ class Settings(BaseModel):
     VWA_ASR_NO_SPEECH: float = Field(0.0, description="no-speech gate: a window whose no-speech probability exceeds this yields an empty final and no partial (0: off; Whisper's customary threshold is 0.6)")
     VWA_ASR_BEAM: int = Field(1, ge=1, le=8, description="beam width of the final recognition passes (1: greedy, the default; 2-8: beam search, csrc/beam -- a final pass then takes this many ASR session slots; partials and speculative passes stay greedy)")
     VWA_ASR_ALTERNATIVES: int = Field(1, ge=1, le=8, description="ranked alternatives a final transcript event carries (Deepgram's alternatives; 1..VWA_ASR_BEAM)")
+    VWA_ASR_LONGFORM: bool = Field(False, description="long utterances: when the 30 s window fills while the speaker is still talking, cut it at the end of the last segment a timestamp pass closes (csrc/tsrules, asr/segments.py) and carry the rest of the audio over, instead of finalising the whole window at an arbitrary sample (0, the default: today's whole-window final)")
+    VWA_ASR_LONGFORM_MIN_S: float = Field(10.0, ge=0.0, le=30.0, description="the earliest segment end, in seconds from the window's start, a long-form cut is taken at; an earlier one is ignored (the window would refill almost at once) and the whole window is finalised. 10 s is a policy default and is NOT tuned on real speech")
     VWA_ASR_KEYTERMS: str = Field("", description="default keyterms of every voice session: a comma list of words or phrases the recogniser should prefer, each with an optional :boost (Deepgram's keyterm; csrc/boost); empty, the default: keyterm boosting is off unless a client names terms (/stream?keyterm=...)")
     VWA_ASR_KEYTERM_BOOST: float = Field(2.0, gt=0.0, le=20.0, description="boost, in logit units (nats), of a keyterm that names none: the odds of its tokens are multiplied by e^boost. In (0, 20]; 2.0 is in the range the shallow-fusion literature commonly uses and is NOT tuned on real speech")
     VWA_CONTEXT_MAX_BYTES: int = Field(2048, description="per-session context cap sent to the brain")

@@ -419,6 +419,12 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
                 st["pending"] = f"{st['pending']} {text}" if st["pending"] else text
                 if st["debounce"] is not None:
                     st["debounce"].cancel()
+                if ev.get("speech_final") is False:
+                    # a long utterance cut at a segment end (asr/streaming.py long-form): the speaker
+                    # is still talking, so the text waits for the final that ends the utterance
+                    st["debounce"] = None
+                    m.inc("longform_finals")
+                    continue
                 start_debounce()
 
         app["live"] += 1
