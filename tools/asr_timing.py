@@ -7,6 +7,7 @@ python tools/asr_timing.py --language auto [--asr whisper-large-v3]   # the pass
 python tools/asr_timing.py --beam 5 [--asr whisper-large-v3]   # beam search against W greedy rows, per token step
 python tools/asr_timing.py --keyterms 50 [--batch-rows 8]   # the boosted step against plain rows
 python tools/asr_timing.py --timestamps [--batch-rows 8]   # the timestamp rules step against plain rows, and the boundary pass
+python tools/asr_timing.py --fallback [--batch-rows 8]   # the scored step against plain rows, and a forced two-attempt pass
 
 decode_us_per_token = host time from the encoder's launch to the last token / tokens (includes the
 encoder and cross K/V projections still running after their launch); decode_gpu_us_per_token = the
@@ -56,6 +57,11 @@ def main():
                          "boost launch of the same run), whole decode steps plain against timestamps for one session "
                          "(the device loop; plain takes the persistent decoder where the model has one) and for "
                          "--batch-rows batched sessions, and the boundary pass of a full 30 s window")
+    ap.add_argument("--fallback", action="store_true",
+                    help="time the quality gate: the score launch alone (1 row and --batch-rows rows), whole decode "
+                         "steps plain against scored for one session (the device loop; plain takes the persistent "
+                         "decoder where the model has one) and for --batch-rows batched sessions, and a final pass "
+                         "forced into two attempts against the same pass with one")
     ap.add_argument("--batch-rows", type=int, default=8)
     ap.add_argument("--small-max-m", type=int, default=None,
                     help="A/B: rows up to which small weights take the one-tile kernel (16: the tiled GEMM above 16)")
@@ -290,6 +296,78 @@ def main():
                               step_overhead_share_rows=round(step["ts_rows"] / step["plain_rows"] - 1.0, 4),
                               boundary_pass_tokens=n_b, boundary_pass_ms=round(statistics.median(tot), 2),
                               boundary_pass_ms_min=round(min(tot), 2), boundary_pass_ms_max=round(max(tot), 2))),
+              flush=True)
+        return
+    if a.fallback:  # decode_many(score= / fallback=): the score launch, scored steps against plain ones, a retry
+        from voice_enabled_browser_automation_amd.asr.fallback import FallbackPolicy
+
+        R = a.batch_rows
+        cfg = m.cfg
+        eng = AsrEngine(m, load_tokenizer("whisper"), max_sessions=R)
+        audio = eng.pcm_to_audio(synth_speech(10.0, seed=100))
+
+        def timed(fn):
+            fn()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+            for e0, e1 in ev:
+                e0.record()
+                fn()
+                e1.record()
+            torch.cuda.synchronize()
+            return statistics.median(e0.elapsed_time(e1) for e0, e1 in ev) * 1e3
+
+        i32 = dict(dtype=torch.int32, device="cuda")
+        enable = torch.ones(R, **i32)
+        tok = torch.full((R,), 1000, **i32)
+        launch = {}
+        for rows in (1, R):
+            x = torch.randn(rows, m.vocab_padded, device="cuda") * 3
+            sm, cn = torch.zeros(rows, device="cuda"), torch.zeros(rows, 2, **i32)
+            lp = torch.zeros(rows, device="cuda")
+            s2, c2 = torch.zeros_like(sm), torch.zeros_like(cn)
+            launch[rows] = timed(lambda: ops.score_step(x, cfg.vocab_size, cfg.eot, eng.mask_text_eot, enable[:rows],
+                                                        tok[:rows], sm, s2, cn, c2, step_lp=lp))
+        res = {}
+        for kind in ("plain_1", "score_1", "plain_rows", "score_rows") * 2:  # interleaved, reps each
+            n = 1 if kind.endswith("_1") else R
+            kw = dict(score=True) if kind.startswith("score") else {}
+            for _ in range(2):
+                eng.decode_many([audio] * n, exact_tokens=a.tokens, **kw)
+            dgpu = []
+            for _ in range(a.reps):
+                eng.decode_many([audio] * n, exact_tokens=a.tokens, **kw)
+                dgpu.append(eng.last_stats.get("decode_gpu_ms") or 0.0)
+            res.setdefault(kind, []).append(statistics.median(dgpu) * 1e3 / a.tokens)
+        step = {k: min(v) for k, v in res.items()}
+        # one final pass (one session) with one attempt -- a threshold every decode passes -- and forced into
+        # two: a threshold none passes and a schedule of two temperatures; the encoder runs once in both
+        one = FallbackPolicy(temperatures=(0.0, 0.2), logprob_threshold=None, compression_ratio_threshold=None)
+        two = FallbackPolicy(temperatures=(0.0, 0.2), logprob_threshold=0.0, compression_ratio_threshold=None)
+        tot = {"one": [], "two": []}
+        dec = {"one": [], "two": []}
+        for name, pol in (("one", one), ("two", two)) * 2:
+            for _ in range(2):
+                eng.decode_many([audio], exact_tokens=a.tokens, fallback=pol)
+            for _ in range(a.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                eng.decode_many([audio], exact_tokens=a.tokens, fallback=pol)
+                tot[name].append((time.perf_counter() - t0) * 1e3)
+                dec[name].append(eng.last_stats.get("decode_gpu_ms") or 0.0)
+            assert eng.last_scores[0]["attempts"] == (1 if name == "one" else 2)
+        print(json.dumps(dict(tool="asr_timing", asr=a.asr, fallback=True, tokens=a.tokens, reps=a.reps, rows=R,
+                              score_launch_us_1_row=round(launch[1], 1), score_launch_us_rows=round(launch[R], 1),
+                              plain_step_us_1=round(step["plain_1"], 1), score_step_us_1=round(step["score_1"], 1),
+                              plain_step_us_rows=round(step["plain_rows"], 1),
+                              score_step_us_rows=round(step["score_rows"], 1),
+                              persistent_used_by_plain=bool(getattr(m, "_wdec", None)),
+                              scored_call_takes_persistent=eng._persistent_loop_ok(None, None, object()),
+                              step_overhead_share_1=round(step["score_1"] / step["plain_1"] - 1.0, 4),
+                              step_overhead_share_rows=round(step["score_rows"] / step["plain_rows"] - 1.0, 4),
+                              one_attempt_pass_ms=round(statistics.median(tot["one"]), 2),
+                              two_attempt_pass_ms=round(statistics.median(tot["two"]), 2),
+                              one_attempt_decode_gpu_ms=round(statistics.median(dec["one"]), 2),
+                              two_attempt_decode_gpu_ms=round(statistics.median(dec["two"]), 2))),
               flush=True)
         return
     if a.language:  # the pass with the fixed default language and with --language (decode_many(languages=))

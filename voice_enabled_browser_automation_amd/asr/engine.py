@@ -374,6 +374,105 @@ class TsRun:
             self.trace[-1].update(kw)
 
 
+class ScoreBuffers:
+    """The engine's transcript score memory (built on the first scored call): one int32 device block
+    of fixed size -- captured loop graphs address it -- and its pinned mirror,
+
+        enable [R] | temperature [R] (f32) | sum0 [R] (f32) | cnt0 [R, 2]
+
+    R = ops.SCORE_MAX_ROWS, plus the work block the launches step in place and ONE device-to-host
+    copy reads:  sum [R] (f32) | cnt [R, 2] | step_lp [R] (f32)."""
+
+    def __init__(self, dev):
+        R = ops.SCORE_MAX_ROWS
+        f32 = torch.float32
+        self.h = torch.zeros(5 * R, dtype=torch.int32, pin_memory=dev.type == "cuda")
+        self.d = torch.zeros(5 * R, dtype=torch.int32, device=dev)
+        self.work = torch.zeros(4 * R, dtype=torch.int32, device=dev)
+
+        def views(t):
+            return t[:R], t[R : 2 * R].view(f32), t[2 * R : 3 * R].view(f32), t[3 * R :].view(R, 2)
+
+        self.h_enable, self.h_temp, self.h_sum0, self.h_cnt0 = views(self.h)
+        self.enable, self.temp, self.sum0, self.cnt0 = views(self.d)
+        w = self.work
+        self.sum, self.cnt, self.step_lp = w[:R].view(f32), w[R : 3 * R].view(R, 2), w[3 * R :].view(f32)
+
+
+class ScoreRun:
+    """One decode_many call's transcript scores: every utterance's temperature, the sums the host
+    holds (sum of log-probabilities, tokens counted, done), and the launches (ops.score_step) the
+    greedy paths make after each sampler launch.  ``trace``: with AsrEngine.keep_score_trace, one
+    entry per launch."""
+
+    def __init__(self, bufs: ScoreBuffers, B: int, cfg, trace: Optional[List[Dict]]):
+        self.b = bufs
+        self.vocab, self.eot = cfg.vocab_size, cfg.eot
+        self.trace = trace
+        self.temps = [0.0] * B          # this attempt's temperature, per utterance
+        self.sums = [0.0] * B           # the host's copy of every utterance's state
+        self.cnts = [[0, 0] for _ in range(B)]
+        self.attempt = 0
+        self.n = 0
+        self.utts: List[int] = []
+        self.fresh = False
+
+    def begin(self, utts: Sequence[int], temperatures: Sequence[float], attempt: int) -> None:
+        """A new attempt for ``utts`` at those temperatures: their sums start again."""
+        self.attempt = attempt
+        for j, t in zip(utts, temperatures):
+            self.temps[j], self.sums[j], self.cnts[j] = float(t), 0.0, [0, 0]
+        self.utts = []
+
+    def stage(self, utts: Sequence[int]) -> None:
+        """Row i is utterance utts[i]: its temperature and the state the host holds for it go to the
+        device (one copy); the next launch reads the staged state."""
+        b = self.b
+        self.n = n = len(utts)
+        assert 1 <= n <= ops.SCORE_MAX_ROWS
+        b.h_enable.zero_()
+        b.h_enable[:n] = 1
+        b.h_temp[:n] = torch.tensor([self.temps[j] for j in utts], dtype=torch.float32)
+        b.h_sum0[:n] = torch.tensor([self.sums[j] for j in utts], dtype=torch.float32)
+        b.h_cnt0[:n] = torch.tensor([self.cnts[j] for j in utts], dtype=torch.int32)
+        b.d.copy_(b.h, non_blocking=True)
+        self.utts = list(utts)
+        self.fresh = True
+
+    def temperature(self, n: int) -> torch.Tensor:
+        return self.b.temp[:n]
+
+    def step(self, x: torch.Tensor, mask: torch.Tensor, tokens: torch.Tensor, first: Optional[bool] = None) -> None:
+        """After the sampler wrote ``tokens``: every row's sum moves on by its token's log-probability
+        -- from the staged state (``first``; None: when ``stage`` ran since the last launch),
+        afterwards in place."""
+        b = self.b
+        n = self.n
+        assert x.shape[0] == n
+        first = self.fresh if first is None else first
+        self.fresh = False
+        si, ci = (b.sum0, b.cnt0) if first else (b.sum, b.cnt)
+        ops.score_step(x, self.vocab, self.eot, mask, b.enable[:n], tokens, si, b.sum, ci, b.cnt, step_lp=b.step_lp)
+        if self.trace is not None:
+            self.trace.append(dict(utts=list(self.utts), attempt=self.attempt, logits=x.cpu().clone(),
+                                   mask=mask.cpu().clone(), tokens=tokens[:n].tolist(),
+                                   temperature=[self.temps[j] for j in self.utts],
+                                   step_lp=b.step_lp[:n].tolist()))
+
+    def read(self) -> None:
+        """The staged rows' states come to the host (one copy of the work block)."""
+        if not self.utts or self.fresh:  # (nothing launched since the stage: the host's copy stands)
+            self.utts = []
+            return
+        R = ops.SCORE_MAX_ROWS
+        h = self.b.work.cpu()
+        sums = h[:R].view(torch.float32).tolist()
+        cnts = h[R : 3 * R].view(R, 2).tolist()
+        for i, j in enumerate(self.utts):
+            self.sums[j], self.cnts[j] = sums[i], cnts[i]
+        self.utts = []
+
+
 class AsrEngine:
     """Whisper transcription with fixed-work decoding options for benchmarking."""
 
@@ -450,6 +549,13 @@ class AsrEngine:
         self.mask_ts_eot: Optional[torch.Tensor] = None
         self.last_segments: List[Optional[List[Dict]]] = []
         self.last_ts_trace: List[Dict] = []
+        # decode_many(score=True / fallback=...): the scores' device memory (ScoreBuffers), built by the
+        # first scored call; per utterance of the last scored call its score entry (asr/fallback.py
+        # score_entry); with keep_score_trace one entry per score launch of the last call (ScoreRun)
+        self._score_bufs: Optional[ScoreBuffers] = None
+        self.last_scores: List[Dict] = []
+        self.last_score_trace: List[Dict] = []
+        self.sample_seed = 0  # a scored call's Gumbel noise: a function of this seed, the attempt and the step
         self.free_slots = list(range(max_sessions - 1, -1, -1))
 
     keep_sot = False  # decode_many: always probe; keep host copies of the SOT logits and language probabilities
@@ -462,6 +568,9 @@ class AsrEngine:
     # and after the rules, the rows' masks and the chosen tokens (host copies); the call then steps
     # from the host, as with keep_boost_trace
     keep_ts_trace = False
+    # decode_many with score / fallback: keep, per step, the logits the sampler read, the rows' mask,
+    # the chosen tokens and their log-probabilities (host copies); the call then steps from the host
+    keep_score_trace = False
 
     def compile_keyterms(self, terms, boost: Optional[float] = None):
         """Text terms (strings, (text, boost) pairs) compiled for this engine's tokenizer: the
@@ -470,11 +579,13 @@ class AsrEngine:
 
         return kt.compile_keyterms(terms, self.tok, self.model.cfg.eot, boost)
 
-    def _persistent_loop_ok(self, boost: Optional[BoostRun], ts: Optional[TsRun] = None) -> bool:
+    def _persistent_loop_ok(self, boost: Optional[BoostRun], ts: Optional[TsRun] = None,
+                            score: Optional[ScoreRun] = None) -> bool:
         """The one routing decision for the persistent one-launch decoder (wdec_loop_step): its
         argmax runs inside the kernel, before anything could bias or ban the logits, so a boosted
-        call and a timestamp call never take it."""
-        return boost is None and ts is None
+        call and a timestamp call never take it; nor does a scored call -- the logits never leave
+        the kernel for the score launch to read, and it draws no temperature."""
+        return boost is None and ts is None and score is None
 
     def _ts_setup(self) -> None:
         """The timestamp masks and buffers, on the first timestamp call."""
@@ -511,8 +622,9 @@ class AsrEngine:
         t = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int16)).to(self.model.device, non_blocking=True)
         return ops.pcm16_to_f32(t, in_rate=rate)
 
-    def _sample(self, logits, allow_eot: bool, mask: Optional[torch.Tensor] = None) -> int:
-        ops.sample(logits, mask=self._mask(allow_eot) if mask is None else mask, temperature=None,
+    def _sample(self, logits, allow_eot: bool, mask: Optional[torch.Tensor] = None,
+                temperature: Optional[torch.Tensor] = None) -> int:
+        ops.sample(logits, mask=self._mask(allow_eot) if mask is None else mask, temperature=temperature,
                    seed=self.d_seed, step=self.d_step, out_tokens=self.d_tok, part_val=self.part_val,
                    part_idx=self.part_idx)
         return int(self.d_tok[0].item())
@@ -522,24 +634,27 @@ class AsrEngine:
     # replayed back to back; the host reads the tokens once per chunk instead of once per token
     # (measured per token before: 5 metadata copies + a host round trip, ~80 us of GPU idle)
     def _loop_step(self, slot: int, allow_eot: bool, boost: Optional[BoostRun] = None,
-                   ts: Optional[TsRun] = None) -> None:
+                   ts: Optional[TsRun] = None, score: Optional[ScoreRun] = None) -> None:
         r = self.runner
         b = r.b
         # whisper-large persistent decoder: embedding, layers, LM head, argmax and advance are ONE
         # launch (models/whisper.py wdec_loop_step)
-        if self._persistent_loop_ok(boost, ts) and self.model.wdec_loop_step(
+        if self._persistent_loop_ok(boost, ts, score) and self.model.wdec_loop_step(
                 b, self.mask_text_eot if allow_eot else self.mask_text, self.d_tok, self.d_step, self.loop_out,
                 self.loop_cnt, 1 + slot * r.bps):
             return
         logits = r._fwd(1)
-        self._advance(logits, slot, allow_eot, boost, ts=ts)
+        self._advance(logits, slot, allow_eot, boost, ts=ts, score=score)
 
     def _advance(self, logits: torch.Tensor, slot: int, allow_eot: bool, boost: Optional[BoostRun] = None,
-                 first: bool = False, ts: Optional[TsRun] = None) -> None:
+                 first: bool = False, ts: Optional[TsRun] = None, score: Optional[ScoreRun] = None) -> None:
         """boost: the row's keyterm biases go onto the logits before the argmax reads them -- the
         staged state's at the ``first`` step (after the prompt), afterwards the automaton moves on
         by the token the previous step left in ``d_tok``, on the device (no host wait).  ts: the
-        timestamp rules follow in the same manner, on the biased logits."""
+        timestamp rules follow in the same manner, on the biased logits.  score: the sampler reads
+        the row's temperature from the engine's fixed score buffers (0: the greedy path of
+        sample.hip, the same as no temperature at all), and the score launch follows it on the
+        logits it read, from the staged sums at the ``first`` step and in place afterwards."""
         b = self.runner.b
         if boost is not None:
             if first:
@@ -552,20 +667,24 @@ class AsrEngine:
                 ts.apply(logits[:1], mask, ())
             else:
                 ts.advance(logits[:1], mask, self.d_tok, ())
-        ops.sample(logits[:1], mask=mask, temperature=None,
+        ops.sample(logits[:1], mask=mask, temperature=None if score is None else score.temperature(1),
                    seed=self.d_seed, step=self.d_step, out_tokens=self.d_tok, part_val=self.part_val,
                    part_idx=self.part_idx)
+        if score is not None:
+            score.step(logits[:1], mask, self.d_tok, first)
         ops.ext().decode_advance(b.tokens, b.positions, b.ctx_lens, b.slots, self.d_tok, self.loop_out,
                                  self.loop_cnt, 1 + slot * self.runner.bps, self.runner.bs)
 
     LOOP_STEPS = 4  # decode steps per replayed loop graph (graph-to-graph launch gap ~10 us per replay)
 
     def _loop_graph(self, slot: int, allow_eot: bool, steps: int = 1, boost: Optional[BoostRun] = None,
-                    ts: Optional[TsRun] = None) -> "torch.cuda.CUDAGraph":
+                    ts: Optional[TsRun] = None, score: Optional[ScoreRun] = None) -> "torch.cuda.CUDAGraph":
         # (a boosted loop is a graph of its own: it holds the boosting launch and not the persistent
         # decoder; it addresses the engine's fixed boosting buffers, so it serves every boosted call.
-        # A timestamp loop likewise: the rules launch, the timestamp masks, the engine's fixed states)
-        key = (slot, allow_eot, steps, boost is not None, ts is not None)
+        # A timestamp loop likewise: the rules launch, the timestamp masks, the engine's fixed states.
+        # A scored loop likewise: the score launch and a sampler that reads the row's temperature from
+        # the engine's fixed score buffers, so one graph serves every attempt at every temperature)
+        key = (slot, allow_eot, steps, boost is not None, ts is not None) + ((True,) if score is not None else ())
         g = self.loop_graphs.get(key)
         if g is None:
             r = self.runner
@@ -578,23 +697,26 @@ class AsrEngine:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                self._loop_step(slot, allow_eot, boost, ts)
+                self._loop_step(slot, allow_eot, boost, ts, score)
             torch.cuda.current_stream().wait_stream(s)
             g = torch.cuda.CUDAGraph()
             if r.pool is None:
                 r.pool = torch.cuda.graph_pool_handle()
             with torch.cuda.graph(g, pool=r.pool):
                 for _ in range(steps):  # identical steps: each reads what the previous advanced
-                    self._loop_step(slot, allow_eot, boost, ts)
+                    self._loop_step(slot, allow_eot, boost, ts, score)
             self.loop_graphs[key] = g
         return g
 
     def _decode_device(self, slot: int, first_logits: torch.Tensor, n_max: int, exact: bool,
                        P: Optional[int] = None, boost: Optional[BoostRun] = None,
-                       ts: Optional[TsRun] = None) -> List[int]:
+                       ts: Optional[TsRun] = None, score: Optional[ScoreRun] = None,
+                       step0: int = 0) -> List[int]:
         """P: the session's prompt length (SOT sequence + any forced prefix) -- the first sampled
         token sits at position P.  boost: the session's staged keyterm run (row 0); the graphs'
-        warm-up step moves its work state, which the first advance sets again from the staged one."""
+        warm-up step moves its work state, which the first advance sets again from the staged one.
+        score: the session's staged score run (row 0), likewise; the warm-up also moves the sampler's
+        step counter, which a scored call therefore sets (``step0``) once the graphs exist."""
         cfg = self.model.cfg
         r = self.runner
         b = r.b
@@ -602,14 +724,16 @@ class AsrEngine:
         n_max = min(n_max, self.loop_out.numel(), r.bps * r.bs - P)
         if n_max <= 0:
             return []
-        g = self._loop_graph(slot, not exact, boost=boost, ts=ts)
+        g = self._loop_graph(slot, not exact, boost=boost, ts=ts, score=score)
         K = self.LOOP_STEPS
-        gk = self._loop_graph(slot, not exact, K, boost=boost, ts=ts) if K > 1 else None
+        gk = self._loop_graph(slot, not exact, K, boost=boost, ts=ts, score=score) if K > 1 else None
+        if score is not None:
+            self.d_step.fill_(step0)
         # row 0 = this session at the last prompt position; the first advance moves it to P
         b.seq_ids[:1].fill_(slot)
         b.positions[:1].fill_(P - 1)
         self.loop_cnt.zero_()
-        self._advance(first_logits, slot, not exact, boost, first=True, ts=ts)
+        self._advance(first_logits, slot, not exact, boost, first=True, ts=ts, score=score)
         out: List[int] = []
         done = 1
         chunk = n_max if exact else 8
@@ -669,7 +793,8 @@ class AsrEngine:
                     words: bool = False, languages: Optional[Sequence[Optional[str]]] = None,
                     task: Optional[str] = None, beam_size: int = 1,
                     keyterms: Optional[Sequence] = None,
-                    timestamps: Optional[Sequence[bool]] = None) -> List[List[int]]:
+                    timestamps: Optional[Sequence[bool]] = None, score: bool = False,
+                    temperatures: Optional[Sequence[float]] = None, fallback=None) -> List[List[int]]:
         """Token ids decoded for each utterance.  ``prefixes[i]``: text tokens forced after the
         SOT sequence (a streaming session's committed transcript -- asr/streaming.py local
         agreement): they are prefilled in the same ragged prompt step as the SOT tokens and only
@@ -721,7 +846,29 @@ class AsrEngine:
         sampler's tokens and are staged again from the host's histories when the rows move up; a
         single session runs the captured device loop with the rules launch in its graph, and does
         not take the persistent one-launch decoder.  None or all false: nothing of the rules library
-        is loaded, allocated or launched."""
+        is loaded, allocated or launched.
+
+        ``score``: every utterance's running score is kept on the device -- one launch per step
+        (ops.score_step; csrc/score/score.h) right after the sampler adds the chosen token's
+        log-probability under the distribution it was drawn from: the logits after the boost and the
+        rules, restricted to the sampler's mask.  ``self.last_scores[i]`` = {sum_logprob, tokens,
+        avg_logprob (Whisper's: sum / (tokens + 1), the EOT's log-probability is in the sum),
+        temperature, attempts, passed, failed_on}.  ``temperatures[i]`` (implies ``score``): utterance
+        i is sampled at that temperature (0: greedy) -- the sampler reads a device tensor of the rows'
+        temperatures; its Gumbel noise is a function of ``self.sample_seed``, the attempt and the step.
+        ``fallback`` (a FallbackPolicy, asr/fallback.py; implies ``score``, excludes ``temperatures``):
+        after a decode the utterances its rule rejects are decoded again at the schedule's next
+        temperature, within this call and on the same slots -- the encoder ran once, the cross K/V
+        stay, only the prompt step and the token loop run again -- until they pass or the schedule
+        ends (the last attempt then stands, ``passed`` false).  An utterance the no-speech gate
+        rejects is not retried.  The sums advance on the device and are staged again from the host's
+        copies when the rows move up (one small copy each way at such a step); a single session runs
+        the captured device loop with the score launch in its graph.  It composes with prefixes,
+        keyterms, timestamps and words (``_align`` runs once, on the returned attempt); with
+        ``beam_size > 1`` the call raises ValueError before anything is launched (the beams carry
+        their own scores: ``last_beams``).  A scored call does not take the persistent one-launch
+        decoder: its logits never leave the kernel -- the same trade as boost and rules.  All off:
+        nothing of the score library is loaded, allocated or launched."""
         t0 = time.perf_counter()
         m = self.model
         B = len(audios)
@@ -733,6 +880,28 @@ class AsrEngine:
         if W > 1 and (B * W > len(self.free_slots) or B * W > ops.BEAM_MAX_ROWS):
             raise RuntimeError(f"{B} utterances of {W} beams exceed the {min(len(self.free_slots), ops.BEAM_MAX_ROWS)} "
                                "free ASR session slots")
+        policy = fallback
+        sc: Optional[ScoreRun] = None
+        temps = [0.0] * B
+        scored = bool(score) or temperatures is not None or policy is not None
+        if scored:
+            from .fallback import FallbackPolicy
+
+            if W > 1:
+                raise ValueError("score / temperatures / fallback: not with beam_size > 1 (the beams carry their own "
+                                 "scores: last_beams)")
+            if policy is not None and not isinstance(policy, FallbackPolicy):
+                raise TypeError(f"fallback: {type(policy).__name__} is not a FallbackPolicy (asr/fallback.py)")
+            if temperatures is not None:
+                if policy is not None:
+                    raise ValueError("temperatures: not with fallback (its schedule sets them)")
+                if len(temperatures) != B:
+                    raise ValueError(f"temperatures: {len(temperatures)} entries for {B} utterances")
+                temps = [float(t) for t in temperatures]
+                if any(not 0.0 <= t <= 2.0 for t in temps):
+                    raise ValueError(f"temperatures: {temps} not all in [0, 2]")
+            if B > ops.SCORE_MAX_ROWS:
+                raise RuntimeError(f"{B} scored utterances exceed {ops.SCORE_MAX_ROWS} rows")
         prefixes = [list(p) for p in prefixes] if prefixes is not None else [[] for _ in range(B)]
         assert len(prefixes) == B
         ts: Optional[TsRun] = None
@@ -767,6 +936,13 @@ class AsrEngine:
             boost = BoostRun(self._boost_bufs, keyterms, m.cfg.vocab_size,
                              self.last_boost_trace if self.keep_boost_trace else None)
             boost.load()
+        if scored:  # (built only now: every check of the call's arguments has passed)
+            if self._score_bufs is None:
+                self._score_bufs = ScoreBuffers(m.device)
+            if self.keep_score_trace:
+                self.last_score_trace = []
+            sc = ScoreRun(self._score_bufs, B, m.cfg, self.last_score_trace if self.keep_score_trace else None)
+            self.d_seed.fill_(int(self.sample_seed))
         r = self.runner
         cap = r.bps * r.bs  # decoder positions per session
         cfg = m.cfg
@@ -806,85 +982,148 @@ class AsrEngine:
             if m.device.type == "cuda":
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
-            if not probe:
-                logits = self._prompt_logits(slots, prompts)
-            elif not any(auto):
-                # the SOT row's logits do not depend on the rows after it: the one prompt step serves
-                logits, sot_logits = self._prompt_logits(slots, prompts, first=True)
-                sot = self._probe(sot_logits)
-            else:
-                logits, sot = self._prompt_auto(slots, prompts, auto)
             outs: List[List[int]] = [[] for _ in range(B)]
-            live = list(range(B))
             n_max = exact_tokens if exact_tokens is not None else max_tokens
             pos = [len(p) for p in prompts]  # next position per session
             limit = [min(n_max, cap - len(p)) for p in prompts]
             beam_ms = None
-            if beam_slots is not None:
-                outs, beam_ms = self._decode_beams(beam_slots, logits, pos, limit, n_max, min_tokens,
-                                                   exact_tokens is not None, boost, forced)
-                live = []
-            elif (B == 1 and self.device_loop and (exact_tokens is not None or min_tokens == 0) and n_max > 0
-                  and not (boost is not None and self.keep_boost_trace)  # (the trace steps from the host)
-                  and not (ts is not None and self.keep_ts_trace)):
-                if boost is not None:
-                    boost.stage([0], [forced[0]])
-                    logits = logits.contiguous()
-                if ts is not None:
-                    ts.stage([0], [[]])
-                    logits = logits.contiguous()
-                outs[0] = self._decode_device(slots[0], logits, limit[0], exact_tokens is not None, P=pos[0],
-                                              boost=boost, ts=ts)
-                live = []
-            staged: Optional[List[int]] = None  # the live rows the device's boosting states are those of
-            ts_staged: Optional[List[int]] = None  # ... the device's timestamp states are those of
-            ts_masks: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # their masks, without / with EOT
-            for i in range(n_max if live else 0):
-                allow_eot = exact_tokens is None and i >= min_tokens
-                if boost is not None:
-                    # batched greedy rows: while the live set stands, every row's automaton moves on by
-                    # the token the sampler left on the device; when a row drops out the rows move up,
-                    # and the states are staged again from the histories the host has anyway
-                    logits = logits.contiguous()
-                    # (the histories are built only where they are read: to stage, or for the trace)
-                    hist = [forced[j] + outs[j] for j in live] if live != staged or boost.trace is not None else ()
-                    if live != staged:
-                        boost.stage(live, hist)
-                        boost.apply(logits, hist)
-                        staged = list(live)
-                    else:
-                        boost.advance(logits, self.d_tok, hist)
-                mask = None
-                if ts is not None:
-                    # the same scheme for the rules' states (the sampled tokens alone: such a row has no
-                    # prefix); every row brings its own mask, text rows the text mask
-                    logits = logits.contiguous()
-                    hist = [outs[j] for j in live] if live != ts_staged or ts.trace is not None else ()
-                    if live != ts_staged:
-                        ts_masks = tuple(torch.cat([self._mask(e, ts_flags[j]) for j in live]) for e in (False, True))
-                        mask = ts_masks[allow_eot]
-                        ts.stage(live, hist)
-                        ts.apply(logits, mask, hist)
-                        ts_staged = list(live)
-                    else:
-                        mask = ts_masks[allow_eot]
-                        ts.advance(logits, mask, self.d_tok, hist)
-                toks = self._sample_rows(logits, allow_eot, mask)
-                if boost is not None:
-                    boost.note(tokens=list(toks), allow_eot=allow_eot)
-                if ts is not None:
-                    ts.note(tokens=list(toks), allow_eot=allow_eot)
-                nxt = []
-                for j, tok in zip(live, toks):
-                    if tok == m.cfg.eot or tok < 0:
-                        continue
-                    outs[j].append(tok)
-                    if len(outs[j]) < limit[j]:
-                        nxt.append(j)
-                live = nxt
-                if not live or i + 1 >= n_max:
-                    break
-                logits = self.runner.step([(slots[j], outs[j][-1], pos[j] + len(outs[j]) - 1) for j in live])
+
+            def decode_pass(utts: List[int], first_pass: bool, step0: int = 0):
+                """The prompt step and the token loop of the utterances ``utts`` (ascending; every
+                utterance of the call at the first pass, the rejected ones at a fallback pass), on
+                their own slots: the encoder's output and the cross K/V stay.  Fills ``outs``."""
+                nonlocal sot
+                sl, pr = [slots[j] for j in utts], [prompts[j] for j in utts]
+                if not (first_pass and probe):
+                    logits = self._prompt_logits(sl, pr)
+                elif not any(auto):
+                    # the SOT row's logits do not depend on the rows after it: the one prompt step serves
+                    logits, sot_logits = self._prompt_logits(sl, pr, first=True)
+                    sot = self._probe(sot_logits)
+                else:
+                    logits, sot = self._prompt_auto(sl, pr, auto)
+                live = list(utts)
+                ms = None
+                if sc is not None:
+                    self.d_step.fill_(step0)
+                if beam_slots is not None:
+                    res, ms = self._decode_beams(beam_slots, logits, pos, limit, n_max, min_tokens,
+                                                 exact_tokens is not None, boost, forced)
+                    outs[:] = res
+                    live = []
+                elif (B == 1 and self.device_loop and (exact_tokens is not None or min_tokens == 0) and n_max > 0
+                      and not (boost is not None and self.keep_boost_trace)  # (the trace steps from the host)
+                      and not (ts is not None and self.keep_ts_trace)
+                      and not (sc is not None and self.keep_score_trace)):
+                    if boost is not None:
+                        boost.stage([0], [forced[0]])
+                        logits = logits.contiguous()
+                    if ts is not None:
+                        ts.stage([0], [[]])
+                        logits = logits.contiguous()
+                    if sc is not None:
+                        sc.stage([0])
+                        logits = logits.contiguous()
+                    outs[0] = self._decode_device(slots[0], logits, limit[0], exact_tokens is not None, P=pos[0],
+                                                  boost=boost, ts=ts, score=sc, step0=step0)
+                    live = []
+                staged: Optional[List[int]] = None  # the live rows the device's boosting states are those of
+                ts_staged: Optional[List[int]] = None  # ... the device's timestamp states are those of
+                ts_masks: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # their masks, without / with EOT
+                sc_staged: Optional[List[int]] = None  # ... the device's score states are those of
+                for i in range(n_max if live else 0):
+                    allow_eot = exact_tokens is None and i >= min_tokens
+                    if boost is not None:
+                        # batched greedy rows: while the live set stands, every row's automaton moves on by
+                        # the token the sampler left on the device; when a row drops out the rows move up,
+                        # and the states are staged again from the histories the host has anyway
+                        logits = logits.contiguous()
+                        # (the histories are built only where they are read: to stage, or for the trace)
+                        hist = [forced[j] + outs[j] for j in live] if live != staged or boost.trace is not None else ()
+                        if live != staged:
+                            boost.stage(live, hist)
+                            boost.apply(logits, hist)
+                            staged = list(live)
+                        else:
+                            boost.advance(logits, self.d_tok, hist)
+                    mask = None
+                    if ts is not None:
+                        # the same scheme for the rules' states (the sampled tokens alone: such a row has no
+                        # prefix); every row brings its own mask, text rows the text mask
+                        logits = logits.contiguous()
+                        hist = [outs[j] for j in live] if live != ts_staged or ts.trace is not None else ()
+                        if live != ts_staged:
+                            ts_masks = tuple(torch.cat([self._mask(e, ts_flags[j]) for j in live]) for e in (False, True))
+                            mask = ts_masks[allow_eot]
+                            ts.stage(live, hist)
+                            ts.apply(logits, mask, hist)
+                            ts_staged = list(live)
+                        else:
+                            mask = ts_masks[allow_eot]
+                            ts.advance(logits, mask, self.d_tok, hist)
+                    temp = None
+                    if sc is not None:
+                        # the same scheme for the scores: when the rows have moved up, the sums the device
+                        # holds come to the host (one copy) and go back in the new order with the rows'
+                        # temperatures (one copy) -- before the sampler, which reads the temperatures
+                        logits = logits.contiguous()
+                        if live != sc_staged:
+                            sc.read()
+                            sc.stage(live)
+                            sc_staged = list(live)
+                        temp = sc.temperature(len(live))
+                    toks = self._sample_rows(logits, allow_eot, mask, temp)
+                    if sc is not None:  # (after the sampler, on the logits and the mask it read)
+                        sc.step(logits, self._mask(allow_eot) if mask is None else mask, self.d_tok)
+                    if boost is not None:
+                        boost.note(tokens=list(toks), allow_eot=allow_eot)
+                    if ts is not None:
+                        ts.note(tokens=list(toks), allow_eot=allow_eot)
+                    nxt = []
+                    for j, tok in zip(live, toks):
+                        if tok == m.cfg.eot or tok < 0:
+                            continue
+                        outs[j].append(tok)
+                        if len(outs[j]) < limit[j]:
+                            nxt.append(j)
+                    live = nxt
+                    if not live or i + 1 >= n_max:
+                        break
+                    logits = self.runner.step([(slots[j], outs[j][-1], pos[j] + len(outs[j]) - 1) for j in live])
+                if sc is not None:
+                    sc.read()
+                return ms
+
+            sot_read = None
+            if sc is None:
+                beam_ms = decode_pass(list(range(B)), True)
+            else:
+                from . import fallback as fb
+
+                attempts = [0]
+                retried = [0]
+
+                def attempt(utts: List[int], T: Optional[float]):
+                    nonlocal sot_read
+                    k = attempts[0]
+                    attempts[0] += 1
+                    sc.begin(utts, [temps[j] if T is None else T for j in utts], k)
+                    for j in utts:
+                        outs[j] = []
+                    decode_pass(utts, k == 0, k << 16)
+                    if k == 0 and policy is not None:
+                        # (the gate's verdicts, and an auto session's detected language token in its prompt)
+                        sot_read = self._read_sot(sot, langs, prompts)
+                    if k > 0:
+                        retried[0] += len(utts)
+                    return [(sc.sums[j], len(outs[j]), self.tok.decode([t for t in outs[j] if t < cfg.eot]))
+                            for j in utts]
+
+                if policy is None:
+                    res = attempt(list(range(B)), None)
+                    scores = [fb.score_entry(s_, n_, temps[j], 1, tx) for j, (s_, n_, tx) in enumerate(res)]
+                else:
+                    scores = fb.run(attempt, B, policy, gated=lambda j: bool(sot_read[j]["gated"]))
             if self._chain_failed():  # results of a timed-out chained launch are invalid: redo
                 retry = True
             t_end = time.perf_counter()
@@ -901,12 +1140,17 @@ class AsrEngine:
                 self.last_stats["boosted"] = sum(k is not None for k in keyterms)
             if ts is not None:
                 self.last_stats["timestamps"] = sum(ts_flags)
+            if sc is not None:
+                self.last_stats.update(scored=B, attempts=attempts[0], retried=retried[0])
             if beam_slots is not None:
                 self.last_stats["beam_size"] = W
                 if beam_ms is not None:
                     self.last_stats["beam_ms"] = beam_ms()
             if not retry:
-                self.last_sot = self._read_sot(sot, langs, prompts)  # (fills in the detected language tokens)
+                # (fills in the detected language tokens; a fallback call has read it after its first attempt)
+                self.last_sot = sot_read if sot_read is not None else self._read_sot(sot, langs, prompts)
+                if sc is not None:
+                    self.last_scores = scores
                 self.last_segments = [segments(o, cfg.no_timestamps + 1, cfg.eot, self.tok) if f else None
                                       for o, f in zip(outs, ts_flags)]
                 if words:
@@ -924,7 +1168,8 @@ class AsrEngine:
                 self.free_slots.extend(reversed(slots + [s for bs_ in beam_slots for s in bs_[1:]]))
         return self.decode_many(audios, prefixes, max_tokens=max_tokens, min_tokens=min_tokens,
                                 exact_tokens=exact_tokens, words=words, languages=languages, task=task,
-                                beam_size=beam_size, keyterms=keyterms, timestamps=timestamps)
+                                beam_size=beam_size, keyterms=keyterms, timestamps=timestamps, score=score,
+                                temperatures=temperatures, fallback=fallback)
 
     def _decode_beams(self, beam_slots: List[List[int]], logits: torch.Tensor, pos: List[int], limit: List[int],
                       n_max: int, min_tokens: int, exact: bool, boost: Optional[BoostRun] = None,
@@ -1302,17 +1547,19 @@ class AsrEngine:
         self.loop_graphs.clear()
         return True
 
-    def _sample_rows(self, logits: torch.Tensor, allow_eot: bool, mask: Optional[torch.Tensor] = None) -> List[int]:
-        """mask: the rows' own allow-bits [n, words] (a call with timestamp rows); None: the text mask."""
+    def _sample_rows(self, logits: torch.Tensor, allow_eot: bool, mask: Optional[torch.Tensor] = None,
+                     temperature: Optional[torch.Tensor] = None) -> List[int]:
+        """mask: the rows' own allow-bits [n, words] (a call with timestamp rows); None: the text mask.
+        temperature: the rows' temperatures, f32 [n] on the device (a scored call); None: greedy."""
         n = logits.shape[0]
         if n == 1:
-            return [self._sample(logits, allow_eot, mask)]
+            return [self._sample(logits, allow_eot, mask, temperature)]
         logits = logits.contiguous()
         if mask is None:
             mask = self._mask(allow_eot).expand(n, -1).contiguous()
         assert n <= self.d_tok.numel()  # (a step has at most max(BUCKETS) rows; d_tok is never replaced)
         part_val = torch.empty(n * 64, dtype=torch.float32, device=logits.device)
         part_idx = torch.empty(n * 64, dtype=torch.int32, device=logits.device)
-        ops.sample(logits, mask=mask, temperature=None, seed=self.d_seed, step=self.d_step, out_tokens=self.d_tok,
-                   part_val=part_val, part_idx=part_idx)
+        ops.sample(logits, mask=mask, temperature=temperature, seed=self.d_seed, step=self.d_step,
+                   out_tokens=self.d_tok, part_val=part_val, part_idx=part_idx)
         return self.d_tok[:n].tolist()

@@ -99,7 +99,9 @@ class Hypothesis:
     (``alternatives``: {"transcript", "confidence" = exp(avg_logprob)}) -- ``confidence`` is then
     the best hypothesis' exp(avg_logprob) unless the words pass set it; from a timestamp pass,
     ``tokens`` holds the timestamp tokens too and ``segments`` the transcript's segments
-    (asr/segments.py: {start, end, tokens, text}, seconds from the window's start)."""
+    (asr/segments.py: {start, end, tokens, text}, seconds from the window's start); from a pass under
+    the quality gate (``fallback=``), ``score``: the engine's score entry of the returned attempt
+    (asr/fallback.py score_entry) -- ``confidence`` is then exp(avg_logprob) unless the words pass set it."""
 
     tokens: List[int] = field(default_factory=list)
     text: str = ""
@@ -110,6 +112,7 @@ class Hypothesis:
     no_speech_prob: Optional[float] = None
     alternatives: List[Dict] = field(default_factory=list)
     segments: List[Dict] = field(default_factory=list)
+    score: Optional[Dict] = None
 
 
 class TextRecognizer:
@@ -156,8 +159,32 @@ class StreamingAsrSession:
                  local_agreement: bool = True, spec_silence_s: Optional[float] = None,
                  noise_mult: Optional[float] = None, words: Optional[bool] = None, language: Optional[str] = None,
                  no_speech_threshold: Optional[float] = None, beam: Optional[int] = None,
-                 alternatives: Optional[int] = None, keyterms=None, longform: Optional[bool] = None):
+                 alternatives: Optional[int] = None, keyterms=None, longform: Optional[bool] = None,
+                 fallback=None, fallback_reject: Optional[bool] = None):
         from ..utils.env import asr_beam_knobs, knob
+
+        # the quality gate and temperature fallback (VWA_ASR_FALLBACK, off by default; asr/fallback.py):
+        # a FallbackPolicy, True (the policy of the VWA_ASR_TEMPERATURES / _LOGPROB_THRESHOLD /
+        # _COMPRESSION_RATIO settings -- Whisper's published defaults, not tuned here on real speech),
+        # False, or None (the VWA_ASR_FALLBACK setting).  Greedy final passes only: partials stay
+        # greedy and unscored, and a beam final carries its beams' own scores
+        if fallback is None:
+            fallback = bool(knob("VWA_ASR_FALLBACK"))
+        if fallback is True:
+            from .fallback import FallbackPolicy, parse_temperatures
+
+            fallback = FallbackPolicy(temperatures=parse_temperatures(knob("VWA_ASR_TEMPERATURES")),
+                                      logprob_threshold=float(knob("VWA_ASR_LOGPROB_THRESHOLD")),
+                                      compression_ratio_threshold=float(knob("VWA_ASR_COMPRESSION_RATIO")))
+        self.fallback = fallback or None
+        self._spec_policy = None
+        if self.fallback is not None:
+            from dataclasses import replace
+
+            # a speculative final gets one attempt, at the schedule's first temperature
+            self._spec_policy = replace(self.fallback, temperatures=self.fallback.temperatures[:1])
+        # VWA_ASR_FALLBACK_REJECT: a final whose last attempt still fails is emitted empty
+        self.fallback_reject = bool(knob("VWA_ASR_FALLBACK_REJECT")) if fallback_reject is None else bool(fallback_reject)
 
         # long utterances (VWA_ASR_LONGFORM, off by default): a full window is cut at the end of the
         # last segment a timestamp pass closes, if that lies at or after VWA_ASR_LONGFORM_MIN_S (a
@@ -230,7 +257,8 @@ class StreamingAsrSession:
         self.stats: Dict[str, float] = {"partials": 0, "finals": 0, "asr_ms": 0.0, "passes": 0,
                                         "committed_tokens": 0, "spec_started": 0, "spec_used": 0,
                                         "spec_discarded": 0, "no_speech": 0, "boosted_passes": 0,
-                                        "longform_cuts": 0, "longform_fallbacks": 0}
+                                        "longform_cuts": 0, "longform_fallbacks": 0, "fallback_passes": 0,
+                                        "fallback_retries": 0, "fallback_rejected": 0, "spec_rejected": 0}
         # on_speculative(text): called (from the recognizer's thread) when a speculative final pass
         # finishes while it still covers the utterance -- the voice server starts the brain on it
         # (voice/server.py: the brain's latency then overlaps the rest of the endpoint wait)
@@ -253,11 +281,14 @@ class StreamingAsrSession:
         self._pcm[self._n : self._n + len(fr)] = fr
         self._n += len(fr)
 
-    def _pass_kw(self, final: bool) -> Dict:
-        """Keywords of a recognition pass: only those of the features that are on."""
+    def _pass_kw(self, final: bool, spec: bool = False) -> Dict:
+        """Keywords of a recognition pass: only those of the features that are on.  ``spec``: the
+        speculative final pass -- under the quality gate it gets one scored attempt, no retries."""
         kw: Dict[str, Any] = {"words": True} if final and self.words else {}
         if final and self.beam > 1:
             kw["beam"] = self.beam
+        elif final and self.fallback is not None:
+            kw["fallback"] = self._spec_policy if spec else self.fallback
         if self.language is not None:
             kw["language"] = self._lang_lock or self.language
         if self.keyterms is not None:
@@ -278,6 +309,11 @@ class StreamingAsrSession:
     def _gated(self, hyp: Hypothesis) -> bool:
         p = getattr(hyp, "no_speech_prob", None)
         return self.no_speech_threshold > 0.0 and p is not None and p > self.no_speech_threshold
+
+    def _failed(self, hyp: Hypothesis) -> bool:
+        """The quality gate rejects the pass's returned attempt."""
+        sc = getattr(hyp, "score", None)
+        return self.fallback is not None and sc is not None and not sc.get("passed", True)
 
     def _lang_kw(self, hyp: Hypothesis) -> Dict:
         lang = getattr(hyp, "language", None) if self.language is not None else None
@@ -333,7 +369,7 @@ class StreamingAsrSession:
         self.stats["spec_started"] += 1
         self._spec_t0 = time.perf_counter()
         fut = recognize_async(self.rec, self.buf.copy(), self.committed if self.local_agreement else (),
-                              **self._pass_kw(True))
+                              **self._pass_kw(True, spec=True))
         self._spec = fut
         if self.on_speculative is not None:
             fut.add_done_callback(self._spec_ready)
@@ -342,8 +378,8 @@ class StreamingAsrSession:
         if self._spec is not fut or fut.cancelled() or fut.exception() is not None:
             return  # (speech resumed meanwhile, or a failed pass: the endpoint runs the final itself)
         try:
-            if self._gated(fut.result()):
-                return  # (no speech in the window: nothing to start the brain on)
+            if self._gated(fut.result()) or self._failed(fut.result()):
+                return  # (no speech in the window, or the quality gate rejects it: nothing to start the brain on)
             self.on_speculative(fut.result().text)
         except Exception:  # noqa: BLE001  (a listener failure must not break recognition)
             pass
@@ -404,19 +440,33 @@ class StreamingAsrSession:
                     self.stats["asr_ms"] += (time.perf_counter() - self._spec_t0) * 1e3
                     self.stats["passes"] += 1
                     self._spec = None
+                    if self._failed(hyp) and not self._gated(hyp):
+                        # its one greedy attempt fails the quality gate: the real final pass runs, with the retries
+                        self.stats["spec_rejected"] += 1
+                        hyp = None
                 except Exception:  # noqa: BLE001  (a failed background pass: run the final now)
                     self._drop_spec()
             if hyp is None:
                 hyp = self._run(final=True)
             kw = {}
             text = hyp.text
+            sc = getattr(hyp, "score", None) if self.fallback is not None else None
+            if sc is not None:
+                self.stats["fallback_passes"] += 1
+                self.stats["fallback_retries"] += max(0, int(sc.get("attempts", 1)) - 1)
             if self._gated(hyp):
                 # Deepgram emits empty finals for noise too; the voice server drops an empty transcript
                 text, kw = "", dict(no_speech_prob=hyp.no_speech_prob)
                 self.stats["no_speech"] += 1
+            elif self.fallback_reject and self._failed(hyp):
+                # every temperature failed the gate: an empty final, so a hallucinated command never reaches the brain
+                text = ""
+                self.stats["fallback_rejected"] += 1
             elif self.words:
                 kw = dict(confidence=getattr(hyp, "confidence", 0.0),
                           words=shift_words(getattr(hyp, "words", None) or [], self.t_offset))
+            if sc is not None and not self.words and text:
+                kw["confidence"] = math.exp(sc["avg_logprob"])  # of the returned attempt
             if self.beam > 1 and not self._gated(hyp):
                 if not self.words:
                     kw["confidence"] = getattr(hyp, "confidence", 0.0)  # exp(avg_logprob) of the best hypothesis
@@ -522,16 +572,21 @@ def _words_knob(words: Optional[bool]) -> bool:
 
 
 def _hypothesis(eng, full: List[int], n_samples: int, al=None, sot: Optional[Dict] = None,
-                beams: Optional[List[Dict]] = None, prefix: Sequence[int] = ()) -> Hypothesis:
+                beams: Optional[List[Dict]] = None, prefix: Sequence[int] = (),
+                score: Optional[Dict] = None) -> Hypothesis:
     """The pass's hypothesis; with its alignment (a words pass) also the words, on the utterance's
     own clock, and the transcript confidence (exp of the mean log-probability of its text tokens);
     with its ``last_sot`` entry the language and the no-speech probability; with its ``last_beams``
     entry (a beam pass: ranked {tokens, sum_logprob, avg_logprob}, ``prefix`` the forced tokens
     before them) the alternatives after the first and the confidence exp(avg_logprob) of the best.
     In a pass with keyterms the beams are scored on the biased logits, so these confidences are
-    those of the biased distribution; the words pass scores the model's own logits."""
+    those of the biased distribution; the words pass scores the model's own logits.  With its
+    ``last_scores`` entry (a pass under the quality gate) the score and the confidence
+    exp(avg_logprob) of the returned attempt."""
     text = eng.tok.decode(full).strip()
     hyp = Hypothesis(full, text)
+    if score is not None:
+        hyp.score, hyp.confidence = dict(score), math.exp(score["avg_logprob"])
     if beams:
         hyp.confidence = math.exp(beams[0]["avg_logprob"])
         hyp.alternatives = [dict(transcript=eng.tok.decode(list(prefix) + list(h["tokens"])).strip(),
@@ -599,8 +654,10 @@ class EngineRecognizer:
 
     def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
                   language: Optional[str] = None, beam: int = 1, keyterms=None,
-                  timestamps: bool = False) -> Hypothesis:
-        """language: this pass's language code or "auto" (None: the engine's default); beam: the
+                  timestamps: bool = False, fallback=None) -> Hypothesis:
+        """fallback: the pass's FallbackPolicy (greedy passes; None: unscored) -- its hypothesis
+        carries the returned attempt's score.
+        language: this pass's language code or "auto" (None: the engine's default); beam: the
         pass's beam width (1: greedy) -- it then takes that many of the engine's session slots;
         keyterms: this pass's keyterms, text terms or a compiled set (None: not boosted);
         timestamps: decode with timestamp tokens, up to half the decoder's context whatever
@@ -622,9 +679,12 @@ class EngineRecognizer:
             kw["words"] = True
         if beam > 1:
             kw["beam_size"] = int(beam)
+        elif fallback is not None:
+            kw["fallback"] = fallback
         toks = self.eng.decode_many([self.eng.pcm_to_audio(pcm)], [prefix], max_tokens=self.max_tokens, **kw)[0]
         return _hypothesis(self.eng, prefix + toks, len(pcm), self.eng.last_alignments[0] if words else None,
-                           _sot_of(self.eng, 0), self.eng.last_beams[0] if beam > 1 else None, prefix)
+                           _sot_of(self.eng, 0), self.eng.last_beams[0] if beam > 1 else None, prefix,
+                           self.eng.last_scores[0] if "fallback" in kw else None)
 
 
 class AsrBatcher:
@@ -679,13 +739,13 @@ class AsrBatcher:
 
     def recognize(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
                   language: Optional[str] = None, beam: int = 1, keyterms=None,
-                  timestamps: bool = False) -> Hypothesis:
+                  timestamps: bool = False, fallback=None) -> Hypothesis:
         return self.recognize_async(pcm, prefix, words=words, language=language, beam=beam,
-                                    keyterms=keyterms, timestamps=timestamps).result()
+                                    keyterms=keyterms, timestamps=timestamps, fallback=fallback).result()
 
     def recognize_async(self, pcm: np.ndarray, prefix: Sequence[int] = (), words: bool = False,
                         language: Optional[str] = None, beam: int = 1, keyterms=None,
-                        timestamps: bool = False) -> Future:
+                        timestamps: bool = False, fallback=None) -> Future:
         """Queue a pass for the next GPU batch; the Future resolves to its Hypothesis.  language:
         this pass's code or "auto" (None: the engine's default); a batch may mix them.  beam: the
         pass's beam width (1: greedy).  A beam pass counts ``beam`` session slots; greedy passes and
@@ -697,10 +757,15 @@ class AsrBatcher:
         split -- the passes past the capacity stay queued; a set that alone exceeds it is refused here.
         timestamps: decode with timestamp tokens (up to half the decoder's context; the hypothesis
         carries the segments).  Such a pass is greedy and carries no prefix or words, and such
-        passes are batched among themselves: a decode_many call of their own."""
+        passes are batched among themselves: a decode_many call of their own.
+        fallback: the pass's FallbackPolicy (None: unscored).  Greedy passes only (a beam or timestamp
+        pass drops it); the passes under one policy are batched among themselves, a decode_many call
+        of their own (<= 64 rows), and their hypotheses carry the returned attempts' scores."""
         beam = int(beam)
         if timestamps:
             prefix, words, beam = (), False, 1
+        if timestamps or beam > 1:
+            fallback = None
         if beam < 1 or beam > min(8, self.max_batch):
             raise ValueError(f"beam = {beam} outside 1..{min(8, self.max_batch)} (the engine's session slots)")
         ks = _compile_keyterms(self.eng, keyterms)
@@ -713,13 +778,13 @@ class AsrBatcher:
                 raise RuntimeError("ASR batcher stopped")
             # (cut to what the decoder forces: the hypothesis is built on the prefix it really used)
             self._q.append((np.array(pcm, dtype=np.int16, copy=True), list(prefix)[: self.eng.max_prefix()], fut,
-                            bool(words) and self.words, language, beam, ks, bool(timestamps)))
+                            bool(words) and self.words, language, beam, ks, bool(timestamps), fallback))
             self._cv.notify()
         return fut
 
     def _take(self) -> Dict[tuple, List[tuple]]:
-        """(under the lock) The queued passes of this round by (beam width, timestamps), in queue
-        order: of each kind as many as the slots hold (a pass of width W counts W; a beam call and a
+        """(under the lock) The queued passes of this round by (beam width, timestamps, fallback
+        policy), in queue order: of each kind as many as the slots hold (a pass of width W counts W; a beam call and a
         timestamp call hold <= 64 rows); the rest stays queued."""
         groups: Dict[tuple, List[tuple]] = {}
         used: Dict[tuple, int] = {}
@@ -727,8 +792,8 @@ class AsrBatcher:
         rest: List[tuple] = []
         for item in self._q:
             w, ks = item[5], item[6]
-            g = (w, item[7])
-            cap = self.max_batch if g == (1, False) else min(self.max_batch, 64)
+            g = (w, item[7], item[8])
+            cap = self.max_batch if g == (1, False, None) else min(self.max_batch, 64)
             fits = used.get(g, 0) + w <= cap
             if fits and ks is not None and ks.key not in sets.setdefault(g, {}):
                 # a set the call does not hold yet: the call's automata must still fit the tables
@@ -765,13 +830,14 @@ class AsrBatcher:
                 if self._stop and not self._q:
                     return
                 groups = self._take()
-            # greedy passes first, then the timestamp passes, then one call per beam width
-            for width, ts in sorted(groups):
-                self._run_batch(groups[(width, ts)], width, ts)
+            # greedy passes first, then the fallback passes (one call per policy), then the timestamp
+            # passes, then one call per beam width
+            for g in sorted(groups, key=lambda g: (g[0], g[1], g[2] is not None, repr(g[2]))):
+                self._run_batch(groups[g], g[0], g[1], g[2])
 
-    def _run_batch(self, batch: List[tuple], beam: int, timestamps: bool = False) -> None:
-        """One decode_many call: the round's greedy passes (beam 1), its timestamp passes, or its
-        beam passes of one width."""
+    def _run_batch(self, batch: List[tuple], beam: int, timestamps: bool = False, fallback=None) -> None:
+        """One decode_many call: the round's greedy passes (beam 1), its passes under one fallback
+        policy, its timestamp passes, or its beam passes of one width."""
         t0 = time.perf_counter()
         if self.busy is not None:
             self.busy.enter()
@@ -797,13 +863,17 @@ class AsrBatcher:
                 for i, (item, t) in enumerate(zip(batch, toks)):
                     item[2].set_result(_ts_hypothesis(self.eng, t, i))
             else:
+                if fallback is not None:
+                    kw["fallback"] = fallback
+                    self.stats["fallback_passes"] = self.stats.get("fallback_passes", 0) + len(batch)
                 toks = self.eng.decode_many(audios, [item[1] for item in batch], **kw)
                 als = self.eng.last_alignments if want else [None] * len(batch)
                 beams = self.eng.last_beams if beam > 1 else [None] * len(batch)
+                scores = self.eng.last_scores if fallback is not None else [None] * len(batch)
                 for i, (item, t, al) in enumerate(zip(batch, toks, als)):
                     p, pre, fut, w = item[:4]
                     fut.set_result(_hypothesis(self.eng, pre + t, len(p), al if w else None, _sot_of(self.eng, i),
-                                               beams[i], pre))
+                                               beams[i], pre, scores[i]))
         except BaseException as e:  # noqa: BLE001  (fail this batch's passes, keep serving)
             for item in batch:
                 if not item[2].done():

@@ -1664,3 +1664,98 @@ def ts_rules_step(logits: torch.Tensor, vocab: int, eot: int, ts_begin: int, max
     # (a missing library raises: there is no other GPU path)
     ts_rules_ext().ts_rules_step(logits, vocab, eot, ts_begin, max_initial, mask, enable, state_in, state_out, tokens)
     return logits
+
+
+# ----------------------------------------------------------------------------- transcript scores
+_SCORE = None
+_SCORE_ERR: Optional[BaseException] = None
+SCORE_MAX_ROWS = 64          # csrc/score/score.h kScoreMaxRows: rows per launch
+SCORE_MAX_VOCAB = 1 << 20    # ... kScoreMaxVocab
+
+
+def score_ext():
+    """Load the transcript score library ``_vwa_score.so`` (once). Raises if unavailable."""
+    global _SCORE, _SCORE_ERR
+    if _SCORE is not None:
+        return _SCORE
+    if _SCORE_ERR is not None:
+        raise RuntimeError(f"native gfx950 transcript score library unavailable: {_SCORE_ERR}") from _SCORE_ERR
+    try:
+        from . import _vwa_score as m  # type: ignore
+
+        _SCORE = m
+        return m
+    except BaseException as e:  # noqa: BLE001
+        _SCORE_ERR = e
+        raise RuntimeError(
+            "native gfx950 transcript score library _vwa_score.so failed to load; build it with "
+            "`python -m voice_enabled_browser_automation_amd.ops.build`"
+        ) from e
+
+
+def score_step(logits: torch.Tensor, vocab: int, eot: int, mask: torch.Tensor, enable: torch.Tensor,
+               tokens: torch.Tensor, sum_in: torch.Tensor, sum_out: torch.Tensor, cnt_in: torch.Tensor,
+               cnt_out: torch.Tensor, *, step_lp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One step of the running transcript scores, after the sampler (csrc/score/score.h has the
+    per-row rule): row r's sum grows by the log-probability of ``tokens[r]`` under f32 ``logits``
+    [>= rows, >= vocab] restricted to the ids ``mask`` allows (the sampler's packed allow-bits,
+    int32 [1 or >= rows, >= ceil(vocab / 32)]; one row: shared).  ``enable`` int32 [rows <= 64]:
+    <= 0 leaves the row's state alone, as do a row that is done and a token outside [0, vocab);
+    ``sum_in`` / ``sum_out`` f32 [>= rows], ``cnt_in`` / ``cnt_out`` int32 [>= rows, 2] = (n, done),
+    where ``sum_out`` may be ``sum_in`` itself and ``cnt_out`` may be ``cnt_in`` itself; ``step_lp``
+    f32 [>= rows]: this step's log-probability per row (0 for a row left alone).  The logits are
+    only read.  One launch on the GPU; host tensors take the Python reference and never load the
+    library.  Returns ``sum_out``."""
+    i32, f32, dev = torch.int32, torch.float32, logits.device
+    if logits.dim() != 2 or logits.dtype != f32 or logits.stride(1) != 1:
+        raise ValueError(f"score_step: logits must be float32 [rows, >= vocab] with contiguous rows, not "
+                         f"{logits.dtype} {tuple(logits.shape)}")
+    if enable.dim() != 1 or enable.dtype != i32 or not enable.is_contiguous() \
+            or not 1 <= enable.numel() <= min(SCORE_MAX_ROWS, logits.shape[0]):
+        raise ValueError(f"score_step: enable must be contiguous int32 [1..{min(SCORE_MAX_ROWS, logits.shape[0])}] (one "
+                         f"per row of the logits), not {enable.dtype} {tuple(enable.shape)}")
+    rows = enable.numel()
+    vocab, eot = int(vocab), int(eot)
+    if not 1 <= vocab <= min(logits.shape[1], SCORE_MAX_VOCAB):
+        raise ValueError(f"score_step: vocab = {vocab} outside [1, {min(logits.shape[1], SCORE_MAX_VOCAB)}] (the logits' "
+                         "row length)")
+    if not 0 <= eot < vocab:
+        raise ValueError(f"score_step: eot = {eot} outside [0, vocab = {vocab})")
+    words = (vocab + 31) // 32
+    if mask.dim() != 2 or mask.dtype != i32 or mask.stride(1) != 1 or mask.shape[1] < words \
+            or not (mask.shape[0] == 1 or mask.shape[0] >= rows):
+        raise ValueError(f"score_step: mask must be int32 [1 or >= {rows}, >= {words}] with contiguous rows, not "
+                         f"{mask.dtype} {tuple(mask.shape)}")
+    vecs = [("tokens", tokens, i32), ("sum_in", sum_in, f32), ("sum_out", sum_out, f32)]
+    if step_lp is not None:
+        vecs.append(("step_lp", step_lp, f32))
+    for name, t, dt in vecs:
+        if t.dim() != 1 or t.dtype != dt or not t.is_contiguous() or t.numel() < rows:
+            raise ValueError(f"score_step: {name} must be contiguous {dt} [>= {rows}], not {t.dtype} {tuple(t.shape)}")
+    for name, t in (("cnt_in", cnt_in), ("cnt_out", cnt_out)):
+        if t.dim() != 2 or t.dtype != i32 or not t.is_contiguous() or t.shape[1] != 2 or t.shape[0] < rows:
+            raise ValueError(f"score_step: {name} must be contiguous int32 [>= {rows}, 2], not {t.dtype} "
+                             f"{tuple(t.shape)}")
+    for name, t in (("mask", mask), ("enable", enable), ("tokens", tokens), ("sum_in", sum_in), ("sum_out", sum_out),
+                    ("cnt_in", cnt_in), ("cnt_out", cnt_out), ("step_lp", step_lp)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"score_step: {name} is on {t.device}, the logits on {dev}")
+    spans = [("sum_in", sum_in, 4 * rows), ("sum_out", sum_out, 4 * rows), ("cnt_in", cnt_in, 8 * rows),
+             ("cnt_out", cnt_out, 8 * rows), ("step_lp", step_lp, 4 * rows)]
+    for i in range(5):
+        for j in range(i + 1, 5):
+            (na, ta, la), (nb, tb, lb) = spans[i], spans[j]
+            if ta is None or tb is None:
+                continue
+            a, b = ta.data_ptr(), tb.data_ptr()
+            if a == b and (i, j) in ((0, 1), (2, 3)):
+                continue
+            if a < b + lb and b < a + la:
+                raise ValueError(f"score_step: {nb} must not overlap {na} (sum_out may be sum_in itself and cnt_out "
+                                 "may be cnt_in itself, nothing else)")
+    if not _gpu(logits):
+        ref.score_step(logits, vocab, eot, mask, enable, tokens, sum_in, sum_out, cnt_in, cnt_out, step_lp)
+        return sum_out
+    # (a missing library raises: there is no other GPU path)
+    score_ext().score_step(logits, vocab, eot, mask, enable, tokens, sum_in, sum_out, cnt_in, cnt_out, step_lp)
+    return sum_out

@@ -11,6 +11,7 @@
 * ``_vwa_beam.so`` -- the beam search steps (``csrc/beam/*.hip`` + its own ``bindings.cpp``), likewise.
 * ``_vwa_boost.so`` -- the keyterm boosting step (``csrc/boost/*.hip`` + its own ``bindings.cpp``), likewise.
 * ``_vwa_tsrules.so`` -- the timestamp rules step (``csrc/tsrules/*.hip`` + its own ``bindings.cpp``), likewise.
+* ``_vwa_score.so`` -- the transcript score step (``csrc/score/*.hip`` + its own ``bindings.cpp``), likewise.
 * ``_vwa_native.so`` -- the CPU runtime library (grammar engine, KV block manager): plain C++17
   with pybind11, built with g++.
 
@@ -40,6 +41,7 @@ SOT_SO = os.path.join(HERE, "_vwa_sot.so")
 BEAM_SO = os.path.join(HERE, "_vwa_beam.so")
 BOOST_SO = os.path.join(HERE, "_vwa_boost.so")
 TSRULES_SO = os.path.join(HERE, "_vwa_tsrules.so")
+SCORE_SO = os.path.join(HERE, "_vwa_score.so")
 
 
 def _torch_paths():
@@ -168,6 +170,11 @@ def build_tsrules(force: bool = False, jobs: int = 8) -> str:
     return _build_kernel_lib("tsrules", TSRULES_SO, "_vwa_tsrules", force, jobs)
 
 
+def build_score(force: bool = False, jobs: int = 8) -> str:
+    """Transcript score library (the sampled tokens' log-probabilities, one launch): csrc/score -> _vwa_score.so."""
+    return _build_kernel_lib("score", SCORE_SO, "_vwa_score", force, jobs)
+
+
 def build_native(force: bool = False) -> str:
     """CPU runtime library (grammar engine + block manager) -- g++ / pybind11."""
     srcs = sorted(glob.glob(os.path.join(CSRC, "runtime", "*.cpp")))
@@ -194,6 +201,7 @@ def build_all(force: bool = False) -> list[str]:
     out.append(build_beam(force))
     out.append(build_boost(force))
     out.append(build_tsrules(force))
+    out.append(build_score(force))
     return out
 
 

@@ -609,3 +609,36 @@ def ts_rules_step(logits, vocab, eot, ts_begin, max_initial, mask, enable, state
             ban(0, ts_begin)
         x[:vocab][banned] = ninf
     return logits, state_out
+
+
+def score_step(logits, vocab, eot, mask, enable, tokens, sum_in, sum_out, cnt_in, cnt_out, step_lp=None):
+    """The score step on host tensors, as csrc/score/score.h states it (the log-sum-exp in f64,
+    rounded to f32 once)."""
+    rows = enable.numel()
+    ninf = float("-inf")
+    old_sum = sum_in[:rows].clone()  # (in place: every row's cells are read before they are written)
+    old_cnt = cnt_in[:rows].clone()
+    ids = torch.arange(vocab)
+    for r in range(rows):
+        t = int(tokens[r])
+        n, done = int(old_cnt[r, 0]), int(old_cnt[r, 1])
+        if int(enable[r]) <= 0 or done != 0 or not 0 <= t < vocab:
+            sum_out[r] = old_sum[r]
+            cnt_out[r] = old_cnt[r]
+            if step_lp is not None:
+                step_lp[r] = 0.0
+            continue
+        m = mask[r if mask.shape[0] > 1 else 0]
+        ok = ((m[ids >> 5] >> (ids & 31)) & 1).bool()
+        x = logits[r, :vocab].double()
+        live = x[ok & (x > ninf)]
+        lp = ninf
+        if bool(ok[t]) and float(x[t]) > ninf and live.numel():
+            lp = min(float(x[t] - torch.logsumexp(live, 0)), 0.0)
+        lp32 = torch.tensor(lp, dtype=torch.float32)
+        sum_out[r] = old_sum[r] + lp32
+        cnt_out[r, 0] = n + 1
+        cnt_out[r, 1] = int(t == eot)
+        if step_lp is not None:
+            step_lp[r] = lp32
+    return sum_out, cnt_out

@@ -122,6 +122,11 @@ class Settings(BaseModel):
     VWA_ASR_ALTERNATIVES: int = Field(1, ge=1, le=8, description="ranked alternatives a final transcript event carries (Deepgram's alternatives; 1..VWA_ASR_BEAM)")
     VWA_ASR_LONGFORM: bool = Field(False, description="long utterances: when the 30 s window fills while the speaker is still talking, cut it at the end of the last segment a timestamp pass closes (csrc/tsrules, asr/segments.py) and carry the rest of the audio over, instead of finalising the whole window at an arbitrary sample (0, the default: today's whole-window final)")
     VWA_ASR_LONGFORM_MIN_S: float = Field(10.0, ge=0.0, le=30.0, description="the earliest segment end, in seconds from the window's start, a long-form cut is taken at; an earlier one is ignored (the window would refill almost at once) and the whole window is finalised. 10 s is a policy default and is NOT tuned on real speech")
+    VWA_ASR_FALLBACK: bool = Field(False, description="Whisper's quality gate and temperature fallback on the final recognition passes: a final whose average token log-probability is below VWA_ASR_LOGPROB_THRESHOLD or whose text compresses better than VWA_ASR_COMPRESSION_RATIO is decoded again at the next of VWA_ASR_TEMPERATURES, on the kept encoder output (csrc/score, asr/fallback.py); a greedy final's confidence is then exp(average log-probability). 0, the default: off, nothing of it is loaded or launched")
+    VWA_ASR_TEMPERATURES: str = Field("0,0.2,0.4,0.6,0.8,1.0", description="the fallback's temperature schedule: a comma list, non-decreasing, each in [0, 2], at most 8 (Whisper's published default)")
+    VWA_ASR_LOGPROB_THRESHOLD: float = Field(-1.0, le=0.0, description="a final whose average token log-probability is below this is rejected. -1.0 is Whisper's published default and is NOT tuned here on real speech")
+    VWA_ASR_COMPRESSION_RATIO: float = Field(2.4, gt=0.0, description="a final whose text's zlib compression ratio exceeds this (a transcript that loops) is rejected. 2.4 is Whisper's published default and is NOT tuned here on real speech")
+    VWA_ASR_FALLBACK_REJECT: bool = Field(False, description="1: a final whose last fallback attempt still fails the quality gate is emitted empty, like a no-speech-gated final, so a hallucinated command never reaches the brain (0, the default: the last attempt is emitted, as Whisper does)")
     VWA_ASR_KEYTERMS: str = Field("", description="default keyterms of every voice session: a comma list of words or phrases the recogniser should prefer, each with an optional :boost (Deepgram's keyterm; csrc/boost); empty, the default: keyterm boosting is off unless a client names terms (/stream?keyterm=...)")
     VWA_ASR_KEYTERM_BOOST: float = Field(2.0, gt=0.0, le=20.0, description="boost, in logit units (nats), of a keyterm that names none: the odds of its tokens are multiplied by e^boost. In (0, 20]; 2.0 is in the range the shallow-fusion literature commonly uses and is NOT tuned on real speech")
     VWA_CONTEXT_MAX_BYTES: int = Field(2048, description="per-session context cap sent to the brain")

@@ -244,14 +244,18 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
         for w in kt_warns:
             m.inc("keyterm_warnings")
             await send({"type": "warn", "payload": f"keyterm: {w}"})
-        boosted_seen = [0]
+        seen = {"boosted_passes": 0, "fallback_passes": 0, "fallback_retries": 0, "fallback_rejected": 0}
 
         def count_boosted():
-            """The session's recognition passes that carried keyterms -> the asr_boosted_passes counter."""
-            n = int((getattr(asr, "stats", None) or {}).get("boosted_passes", 0))
-            if n > boosted_seen[0]:
-                m.inc("asr_boosted_passes", n - boosted_seen[0])
-                boosted_seen[0] = n
+            """The session's recognition passes that carried keyterms -> the asr_boosted_passes counter;
+            its final passes under the quality gate, their retried attempts and the finals the gate
+            emptied -> asr_fallback_passes / asr_fallback_retries / asr_fallback_rejected."""
+            stats = getattr(asr, "stats", None) or {}
+            for k in seen:
+                n = int(stats.get(k, 0))
+                if n > seen[k]:
+                    m.inc("asr_" + k, n - seen[k])
+                    seen[k] = n
 
         async def set_keyterms(payload):
             """The ``keyterms`` control frame: replaces the session's set from the next pass on."""
