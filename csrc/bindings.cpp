@@ -798,7 +798,9 @@ std::tuple<Tensor, int64_t> chain_make(Tensor h, Tensor att, Tensor act, Tensor 
                                        int64_t a_n_splits, OptTensor a_part_o, OptTensor a_part_ml,
                                        OptTensor a_counters, bool w_tiled,
                                        OptTensor a_row_table, OptTensor s_o, OptTensor s_gu, OptTensor s_down,
-                                       OptTensor s_qkv, int64_t tp_ar, OptTensor a_plan, int64_t a_plan_mode) {
+                                       OptTensor s_qkv, int64_t tp_ar, OptTensor a_plan, int64_t a_plan_mode,
+                                       OptTensor p_o, OptTensor p_gu, OptTensor p_down, OptTensor p_qkv,
+                                       std::vector<int64_t> p_base) {
   c10::DeviceGuard g(h.device());
   ChainParams cp{};
   // s_*: per-row scales of fp8 tiled weights (ops.tile_weight_fp8) -> the W8A16 chain
@@ -882,13 +884,36 @@ std::tuple<Tensor, int64_t> chain_make(Tensor h, Tensor att, Tensor act, Tensor 
       cp.attn.plan_mode = (int)a_plan_mode;
     }
   }
+  // p_*: the packed form of each phase's bf16 tiled weight (ops.pack_weight: uint8 [blocks x 3328
+  // bytes | one flag byte per block], p_base: its exponent base), streamed instead of the weight by
+  // the one launch form that decodes it -- attention phase, o_proj in 32-column tiles, one rank;
+  // every other form of the chain ignores them and streams the bf16 weights as before
+  const bool pk = p_o.has_value() && a_q.has_value() && cp.o_nt2 && !s_o.has_value() && !tp_ar && w_tiled &&
+                  w_o.size(0) % 32 == 0;
+  if (pk) {
+    TORCH_CHECK(p_gu.has_value() && p_down.has_value() && p_qkv.has_value() == w_qkv.has_value() &&
+                    (int64_t)p_base.size() == cp.n,
+                "packed chain: every phase's weight needs its packed form and base");
+    const Tensor* pw[4] = {&*p_o, &*p_gu, &*p_down, w_qkv.has_value() ? &*p_qkv : nullptr};
+    for (int i = 0; i < cp.n; ++i) {
+      SkinnyParams& q = cp.ph[i].p;
+      const int64_t blocks = (int64_t)(q.N / 16) * (q.K / 128);
+      check_vec(*pw[i], h, at::kByte, blocks * 3329, "p_* (packed weight)", true);
+      TORCH_CHECK(p_base[i] >= 0 && p_base[i] <= 112, "p_base: an exponent base in 0..112");
+      q.w_pack = pw[i]->data_ptr<uint8_t>();
+      q.w_pack_flag = q.w_pack + blocks * 3328;
+      q.w_pack_base = (int)p_base[i];
+    }
+  }
   int64_t lds = 0;
   Tensor desc = chain_upload(cp, h, lds);
   if (!desc.numel()) return {desc, 0};
   // (bit 24 of the returned LDS size: the down phase streams X with the weights, bit 25: fp8
-  // weights, bit 26: o_proj in 32-column tiles -- chain_run launches that instantiation)
+  // weights, bit 26: o_proj in 32-column tiles, bit 28: packed weights -- chain_run launches that
+  // instantiation)
   return {desc, lds | (cp.n >= 3 && cp.ph[2].xg ? (int64_t)1 << 24 : 0) | (cp.d_nt2 ? (int64_t)1 << 27 : 0) |
-                    (s_o.has_value() ? (int64_t)1 << 25 : 0) | (cp.o_nt2 ? (int64_t)1 << 26 : 0)};
+                    (s_o.has_value() ? (int64_t)1 << 25 : 0) | (cp.o_nt2 ? (int64_t)1 << 26 : 0) |
+                    (pk ? (int64_t)1 << 28 : 0)};
 }
 
 // Whisper decoder chains (skinny_stream.hip chain_kernel SEQ 1 / 2): phase i computes
@@ -955,7 +980,7 @@ void chain_run(Tensor desc, int64_t n_phases, int64_t lds, Tensor like, int64_t 
   check_rc(vwa_chain_launch(reinterpret_cast<const ChainParams*>(desc.data_ptr()), (int)seq, (int)n_phases, (int)attn_g,
                             (int)(lds & 0xFFFFFF), chain_grid(like), cur_stream(like),
                             (int)((lds >> 24) & 1) * (((lds >> 27) & 1) ? 2 : 1), (int)((lds >> 25) & 1),
-                            (int)((lds >> 26) & 1), (int)n_layers),
+                            (int)((lds >> 26) & 1), (int)n_layers, (int)((lds >> 28) & 1)),
            "chain");
 }
 
@@ -1451,7 +1476,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("a_n_splits") = 0, py::arg("a_part_o") = py::none(), py::arg("a_part_ml") = py::none(),
         py::arg("a_counters") = py::none(), py::arg("w_tiled") = false, py::arg("a_row_table") = py::none(),
         py::arg("s_o") = py::none(), py::arg("s_gu") = py::none(), py::arg("s_down") = py::none(),
-        py::arg("s_qkv") = py::none(), py::arg("tp_ar") = 0, py::arg("a_plan") = py::none(), py::arg("a_plan_mode") = 0);
+        py::arg("s_qkv") = py::none(), py::arg("tp_ar") = 0, py::arg("a_plan") = py::none(), py::arg("a_plan_mode") = 0,
+        py::arg("p_o") = py::none(), py::arg("p_gu") = py::none(), py::arg("p_down") = py::none(),
+        py::arg("p_qkv") = py::none(), py::arg("p_base") = std::vector<int64_t>{});
   m.def("set_small_gemm_bytes", &set_small_gemm_bytes);
   m.def("gemm_set_p8", [](int64_t mode) { vwa_gemm_set_p8((int)mode); });
   m.def("skinny_set_x_skew", [](int64_t skew) { vwa_skinny_set_x_skew((int)skew); });

@@ -855,11 +855,77 @@ VWA_DEVICE PhaseRange chain_range(const ChainPhase& ph, int wb0 = 0, int wn = 0)
 // loads per lane (registers (nt * U + u) * 2 + s2, 16 e4m3 each = k 32 g + 16 s2 .. + 16), so an
 // item of the same 16 registers covers twice the k-groups; chain_phase converts them to bf16
 // fragments in registers (v_cvt_scalef32_pk_bf16_fp8) -- W8A16, half the weight bytes
-template <int NT, int U, int WA, int R, bool XG = false, bool F8 = false>
+// PK (packed bf16 weights, SkinnyParams::w_pack): a k-group of a 16-row tile is a 3328-byte block --
+// three 16-byte loads per lane (registers (nt * U + u) * 3 + 0 / 1: low bytes, + 2: exponent codes)
+// and one 4-byte load of sign bits (component nt * U + u of register 12); register 13.x of lane
+// j < NT * U holds the flag byte of the item's k-group j (pack_flag).  13 registers' worth of
+// bytes per item instead of 16; chain_phase rebuilds the bf16 fragments in registers (pack_decode)
+template <int NT, int U>
+VWA_DEVICE unsigned pack_flag(const SkinnyParams& p, int nb, int it, const PhaseRange& r) {
+  const int G = p.K / 128;
+  const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.w_pack_flag), (short)0,
+                                                                     (p.N / 16) * G, 0x00020000);
+  const int lane = VWA_TX & 63;
+  const int unit = r.u0 + it;
+  const int tile = unit / nb, b = unit % nb;
+  const int kg = r.gb + b * U + lane % U;
+  const bool ok = lane < NT * U && it < r.n_items && kg < r.ge;
+  const unsigned off = ok ? (unsigned)((tile * NT + lane / U) * G + kg) : kOOB2;
+  return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rf, (int)off, 0, 0);
+}
+VWA_DEVICE void set_comp(uint4& v, int j, unsigned x) {
+  if (j == 0) v.x = x;
+  else if (j == 1) v.y = x;
+  else if (j == 2) v.z = x;
+  else v.w = x;
+}
+VWA_DEVICE unsigned get_comp(const uint4& v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
+constexpr unsigned kPackBlock = 3328u;  // bytes per packed k-group block
+// bf16 fragment s (elements 8 s .. 8 s + 7 of the lane's 32) of a packed k-group: lo = the low-byte
+// register s >> 1, nib = the fragment's 8 exponent codes, sg = the lane's sign dword, brep = the
+// tensor's base in every byte.  Plain VALU (and / shift / add / v_perm), ~13 operations per 8 weights
+VWA_DEVICE uint4 pack_decode(const uint4& lo, unsigned nib, unsigned sg, int s, unsigned brep) {
+  const unsigned d0 = (s & 1) ? lo.z : lo.x, d1 = (s & 1) ? lo.w : lo.y;
+  // high bytes of elements 0..3 (hx) and 4..7 (hy): sign << 7 | base + code, one element per byte
+  const unsigned hx = ((nib & 0x0F0F0F0Fu) + brep) | ((sg << (7 - 2 * s)) & 0x80808080u);
+  const unsigned hy = (((nib >> 4) & 0x0F0F0F0Fu) + brep) | ((sg << (6 - 2 * s)) & 0x80808080u);
+  uint4 o;  // (v_perm_b32: selector bytes 0..3 pick the second operand's bytes, 4..7 the first's)
+  o.x = __builtin_amdgcn_perm(hx, d0, 0x05010400u);
+  o.y = __builtin_amdgcn_perm(hx, d0, 0x07030602u);
+  o.z = __builtin_amdgcn_perm(hy, d1, 0x05010400u);
+  o.w = __builtin_amdgcn_perm(hy, d1, 0x07030602u);
+  return o;
+}
+
+template <int NT, int U, int WA, int R, bool XG = false, bool F8 = false, bool PK = false>
 VWA_DEVICE void chain_load(const SkinnyParams& p, int nb, uint4 (&wr)[R], int it, const PhaseRange& r, bool wx = true) {
   // (XG: the weights in registers 0 .. 4 NT U - 1, the X fragments from register 8)
-  static_assert(XG ? (NT * U * 4 <= 8 && 8 + U * 4 <= R && !F8) : NT * U * (F8 ? 2 : 4) == R,
+  static_assert(XG ? (NT * U * 4 <= 8 && 8 + U * 4 <= R && !F8 && !PK)
+                   : PK ? (NT * U == 4 && R == 14 && !F8) : NT * U * (F8 ? 2 : 4) == R,
                 "an item fills its register set");
+  if constexpr (PK) {
+    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint8_t*>(p.w_pack), (short)0, (int)((size_t)(p.N / 16) * (p.K / 128) * kPackBlock), 0x00020000);
+    const int lane = VWA_TX & 63;
+    const int unit = r.u0 + it;
+    const int tile = unit / nb, b = unit % nb;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int kg = r.gb + b * U + u;
+      const bool ok = (it < r.n_items) && (kg < r.ge);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const unsigned blk = ((unsigned)(tile * NT + nt) * (unsigned)(p.K / 128) + (unsigned)kg) * kPackBlock;
+        const unsigned vb = ok ? blk + (unsigned)lane * 16u : kOOB2;
+#pragma unroll
+        for (int s = 0; s < 3; ++s) wr[(nt * U + u) * 3 + s] = bload_w_so<WA>(rp, vb, 1024 * s);
+        const unsigned hb = ok ? blk + (unsigned)lane * 4u : kOOB2;
+        set_comp(wr[12], nt * U + u, (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rp, (int)hb, 3072, WA));
+      }
+    }
+    wr[13].x = pack_flag<NT, U>(p, nb, it, r);
+    return;
+  }
   const __amdgpu_buffer_rsrc_t rw =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(p.W), (short)0, (int)((size_t)p.N * p.K * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rxg =
@@ -936,9 +1002,37 @@ VWA_DEVICE void chain_load_x(const SkinnyParams& p, int nb, uint4 (&wr)[R], int 
 // attention and o_proj; the bandwidth-bound gate/up phase then streams one item less per
 // workgroup (measured: 5.5 us per item, tools/chain_probe.py --diag-skip).  Pre-tiled weights.
 // F8: the fp8 tiled item (chain_load F8: two 1 KB loads per k-group, register (nt * U + u) * 2 + s2)
-template <int NT, int U, int WA, bool F8 = false>
+// PK: the packed item (chain_load PK) -- load k of its 12 16-byte loads -> dst + k KB, the sign dwords of
+// k-group j -> dst + 12 KB + 256 j (lane l's 4 bytes at + 4 l); the flag bytes are loaded at read-back
+template <int NT, int U, int WA, bool F8 = false, bool PK = false>
 VWA_DEVICE void chain_preload(const SkinnyParams& p, int nb, const PhaseRange& r, int it, char* dst) {
   static_assert(NT * U * (F8 ? 2 : 4) <= 16, "an item = at most 16 loads of 1 KB per wave (16 KB of LDS)");
+  if constexpr (PK) {
+    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint8_t*>(p.w_pack), (short)0, (int)((size_t)(p.N / 16) * (p.K / 128) * kPackBlock), 0x00020000);
+    const unsigned lane = VWA_TX & 63;
+    char* wd = dst + (VWA_TX >> 6) * 16384;
+    const int unit = r.u0 + it;
+    const int tile = unit / nb, b = unit % nb;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int kg = r.gb + b * U + u;
+      const bool ok = it < r.n_items && kg < r.ge;
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const unsigned blk = ((unsigned)(tile * NT + nt) * (unsigned)(p.K / 128) + (unsigned)kg) * kPackBlock;
+        const unsigned vb = ok ? blk + lane * 16u : kOOB2;
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(
+              rp, (__attribute__((address_space(3))) void*)(wd + ((nt * U + u) * 3 + s) * 1024), 16, vb, 1024 * s, 0, WA);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            rp, (__attribute__((address_space(3))) void*)(wd + 12288 + (nt * U + u) * 256), 4,
+            ok ? blk + lane * 4u : kOOB2, 3072, 0, WA);
+      }
+    }
+    return;
+  }
   const __amdgpu_buffer_rsrc_t rw =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(p.W), (short)0, (int)((size_t)p.N * p.K * 2), 0x00020000);
   const unsigned lane = VWA_TX & 63;
@@ -967,41 +1061,42 @@ VWA_DEVICE void chain_preload(const SkinnyParams& p, int nb, const PhaseRange& r
 // VGPR budget halves with twice the waves).  fp8 (W8A16) items: 8 loads -- with 16 the fp8
 // instantiations ran out of VGPRs at the barrier pre-issue (each new weight register spilled to
 // scratch behind an s_waitcnt vmcnt(0): the item's loads serialised)
-template <int KS, bool F8 = false>
+// packed bf16 (PK): 14 -- 12 registers of 16-byte loads, one of sign dwords, one flag byte
+template <int KS, bool F8 = false, bool PK = false>
 struct ChainShape {
-  static constexpr int R = (KS == 16 || F8) ? 8 : 16;
+  static constexpr int R = PK ? 14 : (KS == 16 || F8) ? 8 : 16;
 };
 
 // W2: a plain phase in 32-column tiles (the chained o_proj, ChainParams::o_nt2; the X-streaming
 // down projection, ChainParams::d_nt2: one k-group of two tiles per item, every X fragment feeds
 // both -- half the X bytes per weight byte)
-template <int EPI, int KS = 8, bool XG = false, bool F8 = false, bool W2 = false>
+template <int EPI, int KS = 8, bool XG = false, bool F8 = false, bool W2 = false, bool PK = false>
 struct PhaseShape {
   static constexpr int NT = (EPI == EPI_SWIGLU || W2) ? 2 : 1;
   // (measured: QKV in half-tile units -- 384 tiles -> 3 units per workgroup, one split tile each --
   // 12.5-13.4 us vs 6.7 median / 11.5 max with whole tiles, also with the split tile processed
   // first and published before the next item's loads under a counted vmcnt)
-  static constexpr int U = XG ? (W2 ? 1 : 2) : ChainShape<KS, F8>::R / 4 / NT * (F8 ? 2 : 1);
+  static constexpr int U = XG ? (W2 ? 1 : 2) : PK ? 4 / NT : ChainShape<KS, F8>::R / 4 / NT * (F8 ? 2 : 1);
 };
 
 // the phase's first weight item (and with pre2 its second) before the barrier wait: a
 // workgroup that arrives early keeps HBM busy while the grid catches up
-template <int EPI, int KS, int WA, bool XG = false, bool F8 = false, bool W2 = false, int R>
+template <int EPI, int KS, int WA, bool XG = false, bool F8 = false, bool W2 = false, bool PK = false, int R>
 VWA_DEVICE void chain_issue_first(const ChainPhase& ph, uint4 (&wr)[R], uint4 (&wr2)[R], int pre2, int wb0 = 0,
                                   int wn = 0) {
-  using S = PhaseShape<EPI, KS, XG, F8, W2>;
+  using S = PhaseShape<EPI, KS, XG, F8, W2, PK>;
   const PhaseRange r = chain_range<KS>(ph, wb0, wn);
   // (issued before the barrier wait: XG items without their X fragments, chain_phase adds them)
-  chain_load<S::NT, S::U, WA, R, XG, F8>(ph.p, ph.nb, wr, 0, r, !XG);
-  if (pre2) chain_load<S::NT, S::U, WA, R, XG, F8>(ph.p, ph.nb, wr2, 1, r, !XG);
+  chain_load<S::NT, S::U, WA, R, XG, F8, PK>(ph.p, ph.nb, wr, 0, r, !XG);
+  if (pre2) chain_load<S::NT, S::U, WA, R, XG, F8, PK>(ph.p, ph.nb, wr2, 1, r, !XG);
 }
 
 // one weight item `it` of a phase into wr (the next phase's item 0 / item 1, see chain_kernel)
-template <int EPI, int KS, int WA, bool XG = false, bool F8 = false, bool W2 = false, int R>
+template <int EPI, int KS, int WA, bool XG = false, bool F8 = false, bool W2 = false, bool PK = false, int R>
 VWA_DEVICE void chain_issue_item(const ChainPhase& ph, uint4 (&wr)[R], int it, int wb0 = 0, int wn = 0) {
-  using S = PhaseShape<EPI, KS, XG, F8, W2>;
+  using S = PhaseShape<EPI, KS, XG, F8, W2, PK>;
   const PhaseRange r = chain_range<KS>(ph, wb0, wn);
-  chain_load<S::NT, S::U, WA, R, XG, F8>(ph.p, ph.nb, wr, it, r);
+  chain_load<S::NT, S::U, WA, R, XG, F8, PK>(ph.p, ph.nb, wr, it, r);
 }
 
 // partial tile of a split tile: cross-wave sums of this workgroup's units -> slot (sc1)
@@ -1031,10 +1126,10 @@ VWA_DEVICE void tile_publish(int M, float* red, f32x4 (&acc)[NT], float* slot) {
 // queued behind weight loads; the other waves issue their item 1 at once (pre2 == 0: one item at
 // the barrier), which streams while the X rows arrive.  hs = items the staging wave has already
 // issued into (X0, X1).
-template <int EPI, int KS, int WA, bool XG = false, bool F8 = false, bool W2 = false, int R>
+template <int EPI, int KS, int WA, bool XG = false, bool F8 = false, bool W2 = false, bool PK = false, int R>
 VWA_DEVICE void chain_phase(const ChainParams& cp, int i, uint4 (&X0)[R], uint4 (&X1)[R], char* smem, int pre2,
                             int hs = 0, int wb0 = 0, int wn = 0, bool has0 = true) {
-  constexpr int NT = PhaseShape<EPI, KS, XG, F8, W2>::NT, U = PhaseShape<EPI, KS, XG, F8, W2>::U;
+  constexpr int NT = PhaseShape<EPI, KS, XG, F8, W2, PK>::NT, U = PhaseShape<EPI, KS, XG, F8, W2, PK>::U;
   const ChainPhase& ph = cp.ph[i];
   const SkinnyParams& p = ph.p;
   const int nb = ph.nb, M = p.M, K = p.K;
@@ -1087,8 +1182,8 @@ VWA_DEVICE void chain_phase(const ChainParams& cp, int i, uint4 (&X0)[R], uint4 
   const bool xw = xdma && cp.xwait;
   if (xdma && cp.xfirst && !xw) lds_sync();
   auto issue_rest = [&]() {
-    if (xdma && !stager && !has0) chain_load<NT, U, WA, R, XG, F8>(p, nb, X0, 0, r);  // (not issued at the barrier)
-    if (xdma && !stager && (!pre2 || !has0)) chain_load<NT, U, WA, R, XG, F8>(p, nb, X1, 1, r);  // streams during the staging
+    if (xdma && !stager && !has0) chain_load<NT, U, WA, R, XG, F8, PK>(p, nb, X0, 0, r);  // (not issued at the barrier)
+    if (xdma && !stager && (!pre2 || !has0)) chain_load<NT, U, WA, R, XG, F8, PK>(p, nb, X1, 1, r);  // streams during the staging
   };
   if (!xw) issue_rest();
 
@@ -1099,15 +1194,19 @@ VWA_DEVICE void chain_phase(const ChainParams& cp, int i, uint4 (&X0)[R], uint4 
   } else if (stager) {
     int nw = 0;
     if (hs < 1) {
-      chain_load<NT, U, WA, R, XG, F8>(p, nb, X0, 0, r);
+      chain_load<NT, U, WA, R, XG, F8, PK>(p, nb, X0, 0, r);
       ++nw;
     }
     if (hs < 2) {
-      chain_load<NT, U, WA, R, XG, F8>(p, nb, X1, 1, r);
+      chain_load<NT, U, WA, R, XG, F8, PK>(p, nb, X1, 1, r);
       ++nw;
     }
-    // the pieces are older than the nw weight items (16 loads each): wait for them only
-    if constexpr (R == 16) {
+    // the pieces are older than the nw weight items (16 loads each; packed: 17): wait for them only
+    if constexpr (PK) {
+      if (nw == 2) asm volatile("s_waitcnt vmcnt(34)" ::: "memory");
+      else if (nw == 1) asm volatile("s_waitcnt vmcnt(17)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else if constexpr (R == 16) {
       if (nw == 2) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
       else if (nw == 1) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1131,8 +1230,8 @@ VWA_DEVICE void chain_phase(const ChainParams& cp, int i, uint4 (&X0)[R], uint4 
   auto issue_xw = [&]() {
     issue_rest();
     if (stager) {
-      if (hs < 1) chain_load<NT, U, WA, R, XG, F8>(p, nb, X0, 0, r);
-      if (hs < 2) chain_load<NT, U, WA, R, XG, F8>(p, nb, X1, 1, r);
+      if (hs < 1) chain_load<NT, U, WA, R, XG, F8, PK>(p, nb, X0, 0, r);
+      if (hs < 2) chain_load<NT, U, WA, R, XG, F8, PK>(p, nb, X1, 1, r);
     }
     if (r.n_items > 0) epi_values<EPI, NT, true>(p, first_tile, VWA_TX, pre);
   };
@@ -1170,8 +1269,15 @@ VWA_DEVICE void chain_phase(const ChainParams& cp, int i, uint4 (&X0)[R], uint4 
   f32x4 acc[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // packed weights: the tensor's base in every byte, and the bf16 copy for flagged k-groups
+  const unsigned brep = PK ? (unsigned)p.w_pack_base * 0x01010101u : 0u;
+  const __amdgpu_buffer_rsrc_t rw16 = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<u16*>(p.W), (short)0, PK ? (int)((size_t)p.N * p.K * 2) : 0, 0x00020000);
   auto compute = [&](const uint4 (&wr)[R], int it) {
     const int b = (r.u0 + it) % nb;
+    // (PK) bit j: k-group j = nt * U + u of this item holds a value the code cannot express
+    unsigned flagged = 0;
+    if constexpr (PK) flagged = (unsigned)__ballot(wr[13].x != 0u);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int kg = r.gb + b * U + u;
@@ -1193,6 +1299,16 @@ VWA_DEVICE void chain_phase(const ChainParams& cp, int i, uint4 (&X0)[R], uint4 
             bw.y = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, true));
             bw.z = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, false));
             bw.w = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, true));
+            acc[nt] = mfma16(as_bf16x8(a), as_bf16x8(bw), acc[nt]);
+          } else if constexpr (PK) {
+            const int j = nt * U + u;
+            uint4 bw;
+            if ((flagged >> j) & 1u) {  // wave-uniform, ~1 k-group in 10^5: the fragment from the bf16 copy
+              const unsigned T = (unsigned)(((r.u0 + it) / nb) * NT + nt);
+              bw = bload(rw16, ((T * (unsigned)(K / 128) + (unsigned)kg) * 4u + (unsigned)s) * 1024u + (unsigned)lane * 16u);
+            } else {
+              bw = pack_decode(wr[j * 3 + (s >> 1)], get_comp(wr[j * 3 + 2], s), get_comp(wr[12], j), s, brep);
+            }
             acc[nt] = mfma16(as_bf16x8(a), as_bf16x8(bw), acc[nt]);
           } else {
             acc[nt] = mfma16(as_bf16x8(a), as_bf16x8(wr[(nt * U + u) * 4 + s]), acc[nt]);
@@ -1245,7 +1361,7 @@ VWA_DEVICE void chain_phase(const ChainParams& cp, int i, uint4 (&X0)[R], uint4 
     if (unit % nb != nb - 1 && it != r.n_items - 1) return false;
     return !(tile * nb >= r.u0 && (tile + 1) * nb <= u1);
   };
-  if (!pre2 && !xdma) chain_load<NT, U, WA, R, XG, F8>(p, nb, X1, 1, r);
+  if (!pre2 && !xdma) chain_load<NT, U, WA, R, XG, F8, PK>(p, nb, X1, 1, r);
   auto ldi = [&](uint4 (&wr)[R], int idx) {
     if (idx == 2 && ((i == 1 && cp.lds_item && w < cp.lds_item_waves) ||
                      (i == 2 && cp.lds_item2 && w < cp.lds_item2_waves && !(cp.poll_free && w == 0)))) {  // preloaded (chain_preload)
@@ -1254,11 +1370,20 @@ VWA_DEVICE void chain_phase(const ChainParams& cp, int i, uint4 (&X0)[R], uint4 
       // the compiler does not order LDS-DMA writes before these reads)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       const char* src = smem + (i == 1 ? cp.lds_item : cp.lds_item2) + w * 16384 + lane * 16;
+      if constexpr (PK) {  // (chain_preload PK: 12 KB of 16-byte loads, then 4 x 256 B of sign dwords)
+#pragma unroll
+        for (int k = 0; k < 12; ++k) wr[k] = *reinterpret_cast<const uint4*>(src + k * 1024);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          set_comp(wr[12], j, *reinterpret_cast<const unsigned*>(src - lane * 12 + 12288 + j * 256));
+        wr[13].x = pack_flag<NT, U>(p, nb, idx, r);
+        return;
+      }
 #pragma unroll
       for (int k = 0; k < R; ++k) wr[k] = *reinterpret_cast<const uint4*>(src + k * 1024);
       return;
     }
-    chain_load<NT, U, WA, R, XG, F8>(p, nb, wr, idx, r);
+    chain_load<NT, U, WA, R, XG, F8, PK>(p, nb, wr, idx, r);
   };
   for (int it = 0; it < n_pad; it += 2) {
     compute(X0, it);
@@ -1403,10 +1528,12 @@ VWA_DEVICE void kv_prefetch(const DecodeAttnParams& a, int ev, unsigned char* ld
 // (Skipping the wait is safe for the ticket barriers: such a workgroup's next arrival happens only
 // after the attention hand-off, which itself needed this barrier complete.)
 template <int KS, int SEQ, int NPH, int AG, int WA, bool XG2 = false, bool F8 = false, bool O2 = false, bool D2 = false,
-          bool MULTI = false>
+          bool MULTI = false, bool PK = false>
 __global__ __launch_bounds__(KS * 64) void chain_kernel(const ChainParams* __restrict__ cpp, int n_layers) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   static_assert(!MULTI || (SEQ == 0 && NPH == 4 && AG > 0 && !XG2), "multi-layer launch: Llama tails with attention");
+  // PK: every phase streams the packed form of its bf16 weights (SkinnyParams::w_pack)
+  static_assert(!PK || (SEQ == 0 && AG > 0 && O2 && !XG2 && !F8), "packed weights: the bf16 Llama tail with attention");
   const int nwg = (int)gridDim.x;
   unsigned long long* bar = reinterpret_cast<unsigned long long*>(cpp->bar);
   unsigned long long bar_next = chain_base(bar, nwg, cpp->bar_mode);  // mode >= 4: running target
@@ -1435,10 +1562,10 @@ __global__ __launch_bounds__(KS * 64) void chain_kernel(const ChainParams* __res
   pf_prev = pf_next;
   pf_next = false;
   const ChainParams& cp = cpp[li];  // device-resident descriptor
-  // Warm the scalar cache with the whole descriptor (25 x 64-byte lines) in ONE round trip: the
+  // Warm the scalar cache with the whole descriptor (26 x 64-byte lines) in ONE round trip: the
   // fields are otherwise fetched behind branches and earlier fields' values, a chain of dependent
   // scalar misses (the attention prologue measured ~6 of them before its first vector load)
-  static_assert(sizeof(ChainParams) <= 25 * 64, "descriptor warm-up covers 25 lines");
+  static_assert(sizeof(ChainParams) == 26 * 64, "descriptor warm-up covers exactly the descriptor's 26 lines");
   {
     // (non-volatile, no memory clobber: a volatile block counts as a memory write and turns every
     // later descriptor read into a vector load; the never-true test keeps it alive)
@@ -1449,6 +1576,7 @@ __global__ __launch_bounds__(KS * 64) void chain_kernel(const ChainParams* __res
         "s_load_dword %0, %1, 0x300\n\t""s_load_dword %0, %1, 0x340\n\t""s_load_dword %0, %1, 0x380\n\t""s_load_dword %0, %1, 0x3c0\n\t"
         "s_load_dword %0, %1, 0x400\n\t""s_load_dword %0, %1, 0x440\n\t""s_load_dword %0, %1, 0x480\n\t""s_load_dword %0, %1, 0x4c0\n\t""s_load_dword %0, %1, 0x500\n\t"
         "s_load_dword %0, %1, 0x540\n\t""s_load_dword %0, %1, 0x580\n\t""s_load_dword %0, %1, 0x5c0\n\t""s_load_dword %0, %1, 0x600\n\t"
+        "s_load_dword %0, %1, 0x640\n\t"
         "s_waitcnt lgkmcnt(0)"
         : "=&s"(junk)
         : "s"(cpp + li));
@@ -1457,7 +1585,7 @@ __global__ __launch_bounds__(KS * 64) void chain_kernel(const ChainParams* __res
   // (zeroed per layer: otherwise a path that reads a set before writing it -- only possible for
   // an all-OOB padding item -- keeps the previous layer's 128 registers live across the layer
   // loop's back edge and through the attention: spills.  Zeros cost nothing to rematerialise.)
-  uint4 A[ChainShape<KS, F8>::R] = {}, B[ChainShape<KS, F8>::R] = {};
+  uint4 A[ChainShape<KS, F8, PK>::R] = {}, B[ChainShape<KS, F8, PK>::R] = {};
   // barrier = arrive (stores drained), issue the next phase's first weight item, then wait: the
   // weight stream is in flight while the slowest workgroup finishes
   unsigned long long gen;
@@ -1490,14 +1618,14 @@ __global__ __launch_bounds__(KS * 64) void chain_kernel(const ChainParams* __res
   // swapping the sets per path measured 120 B of VGPR spills)
   auto issue0 = [&](int pre) {
     if (nx) {
-      chain_issue_item<E0, KS, WA, false, F8, O2>(cp.ph[0], B, 0, ob0, on);
-      chain_issue_item<E1, KS, WA, false, F8>(cp.ph[1], A, 0);
+      chain_issue_item<E0, KS, WA, false, F8, O2, PK>(cp.ph[0], B, 0, ob0, on);
+      chain_issue_item<E1, KS, WA, false, F8, false, PK>(cp.ph[1], A, 0);
     } else {
-      chain_issue_first<E0, KS, WA, false, F8, O2>(cp.ph[0], B, A, pre, ob0, on);
+      chain_issue_first<E0, KS, WA, false, F8, O2, PK>(cp.ph[0], B, A, pre, ob0, on);
     }
   };
   auto preload1 = [&]() {
-    chain_preload<PhaseShape<E1, KS, false, F8>::NT, PhaseShape<E1, KS, false, F8>::U, WA, F8>(
+    chain_preload<PhaseShape<E1, KS, false, F8, false, PK>::NT, PhaseShape<E1, KS, false, F8, false, PK>::U, WA, F8, PK>(
         cp.ph[1].p, cp.ph[1].nb, chain_range<KS>(cp.ph[1]), 2, smem + cp.lds_item);
   };
   if constexpr (AG > 0) {
@@ -1523,7 +1651,7 @@ __global__ __launch_bounds__(KS * 64) void chain_kernel(const ChainParams* __res
                                                           if constexpr (F8) {
                                                             if (cp.attn_pre && cp.osub && n_attn > 0 && n_attn <= nwg / 2 &&
                                                                 (int)blockIdx.x < n_attn) {
-                                                              chain_issue_item<E1, KS, WA, false, F8>(cp.ph[1], A, 0);
+                                                              chain_issue_item<E1, KS, WA, false, F8, false, PK>(cp.ph[1], A, 0);
                                                               apre = true;
                                                             }
                                                           }
@@ -1602,7 +1730,7 @@ __global__ __launch_bounds__(KS * 64) void chain_kernel(const ChainParams* __res
     // wave's item 1 unloaded whenever an attention workgroup also had >= 2 o_proj items -- more
     // attention items than half the grid: several sessions' rows, or a grid cut by
     // VWA_CHAIN_GRID_DIV -- and its MFMAs read stale registers: NaN / wrong o_proj tiles.)
-    chain_phase<E0, KS, WA, false, F8, O2>(cp, 0, B, A, smem, nx ? 1 : pre0, nx ? 2 : 1 + (pre0 ? 1 : 0), ob0, on);
+    chain_phase<E0, KS, WA, false, F8, O2, PK>(cp, 0, B, A, smem, nx ? 1 : pre0, nx ? 2 : 1 + (pre0 ? 1 : 0), ob0, on);
   stamp();
   if (SEQ == 0 && tpr) chain_tp_reduce(cp, 0, er + 1, bar, nwg, bar_next);
   gen = chain_arrive(bar, nwg, cp.bar_mode, bar_next);
@@ -1612,8 +1740,8 @@ __global__ __launch_bounds__(KS * 64) void chain_kernel(const ChainParams* __res
   const bool prew = (cp.pre_waves == 0 || wv < cp.pre_waves) && !(cp.poll_free && wv == 0);
   const bool nx1 = nx || apre;  // phase 1's item 0 already in A (o_proj's free set, or the attention window)
   if (!stg) {
-    if (nx1) chain_issue_item<E1, KS, WA, false, F8>(cp.ph[1], B, 1);  // phase 1's item 0 is already in A
-    else if (prew) chain_issue_first<E1, KS, WA, false, F8>(cp.ph[1], A, B, preb_of(1));
+    if (nx1) chain_issue_item<E1, KS, WA, false, F8, false, PK>(cp.ph[1], B, 1);  // phase 1's item 0 is already in A
+    else if (prew) chain_issue_first<E1, KS, WA, false, F8, false, PK>(cp.ph[1], A, B, preb_of(1));
   }
   chain_wait(bar, gen, cp.bar_mode);
   // every attention output was counted and every waiter released before this barrier: reset the
@@ -1621,20 +1749,20 @@ __global__ __launch_bounds__(KS * 64) void chain_kernel(const ChainParams* __res
   if (AG > 0 && cp.attn_flag && blockIdx.x == 0 && VWA_TX == 0)
     __hip_atomic_store(gp(&bar[kBarAttnDone]), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   stamp();
-  chain_phase<E1, KS, WA, false, F8>(cp, 1, A, B, smem, nx1 ? 1 : preb_of(1), nx1 ? 1 : 0, 0, 0, nx1 || prew);
+  chain_phase<E1, KS, WA, false, F8, false, PK>(cp, 1, A, B, smem, nx1 ? 1 : preb_of(1), nx1 ? 1 : 0, 0, 0, nx1 || prew);
   stamp();
   if constexpr (NPH >= 3) {
     gen = chain_arrive(bar, nwg, cp.bar_mode, bar_next);
-    if ((!stg && prew) || XG2) chain_issue_first<E2, KS, WA, XG2, F8, D2>(cp.ph[2], A, B, preb_of(2));  // (XG2: no staging wave)
+    if ((!stg && prew) || XG2) chain_issue_first<E2, KS, WA, XG2, F8, D2, PK>(cp.ph[2], A, B, preb_of(2));  // (XG2: no staging wave)
     // phase 2's LDS item (down projection): its item 2 streams through the barrier window too
     // (phase 1's LDS use ended at the arrival's __syncthreads; the region lies above phase 2's
     // X rows and scratch, which the staging wave fills after the release)
     if (cp.lds_item2 && wv < cp.lds_item2_waves && !(cp.poll_free && wv == 0))
-      chain_preload<PhaseShape<E2, KS, false, F8>::NT, PhaseShape<E2, KS, false, F8>::U, WA, F8>(
+      chain_preload<PhaseShape<E2, KS, false, F8, false, PK>::NT, PhaseShape<E2, KS, false, F8, false, PK>::U, WA, F8, PK>(
           cp.ph[2].p, cp.ph[2].nb, chain_range<KS>(cp.ph[2]), 2, smem + cp.lds_item2);
     chain_wait(bar, gen, cp.bar_mode);
     stamp();
-    chain_phase<E2, KS, WA, XG2, F8, D2>(cp, 2, A, B, smem, preb_of(2), 0, 0, 0, prew || XG2);
+    chain_phase<E2, KS, WA, XG2, F8, D2, PK>(cp, 2, A, B, smem, preb_of(2), 0, 0, 0, prew || XG2);
     stamp();
     if (SEQ == 0 && tpr) {
       chain_tp_reduce(cp, 1, er + 2, bar, nwg, bar_next);
@@ -1645,10 +1773,10 @@ __global__ __launch_bounds__(KS * 64) void chain_kernel(const ChainParams* __res
   if constexpr (NPH >= 4) {
    if (!MULTI || cp.n >= 4) {  // (MULTI: the model's last layer has no next QKV phase)
     gen = chain_arrive(bar, nwg, cp.bar_mode, bar_next);
-    if (!stg && prew) chain_issue_first<E3, KS, WA, false, F8>(cp.ph[3], A, B, preb_of(3));
+    if (!stg && prew) chain_issue_first<E3, KS, WA, false, F8, false, PK>(cp.ph[3], A, B, preb_of(3));
     chain_wait(bar, gen, cp.bar_mode);
     stamp();
-    chain_phase<E3, KS, WA, false, F8>(cp, 3, A, B, smem, preb_of(3), 0, 0, 0, prew);
+    chain_phase<E3, KS, WA, false, F8, false, PK>(cp, 3, A, B, smem, preb_of(3), 0, 0, 0, prew);
     stamp();
    }
   }
@@ -1723,6 +1851,14 @@ extern "C" int vwa_chain_prepare(ChainParams* cp, int grid) {
     const bool f8 = p.w_scale != nullptr;
     if (f8 && (!p.w_tiled || cp->seq != 0)) return -10;
     if (i > 0 && f8 != (cp->ph[0].p.w_scale != nullptr)) return -10;
+    // packed bf16 weights (w_pack): every phase or none (one kernel instantiation), next to the
+    // tiled bf16 copy the flagged k-groups are read from; the Llama tail with the attention phase and
+    // o_proj in 32-column tiles (checked below, once o_nt2 is settled), <= 4 rows, one rank
+    const bool pk = p.w_pack != nullptr;
+    if (i > 0 && pk != (cp->ph[0].p.w_pack != nullptr)) return -10;
+    if (pk && (f8 || !p.w_tiled || !p.w_pack_flag || p.w_pack_base < 0 || p.w_pack_base > 112 || cp->seq != 0 ||
+               cp->attn_g == 0 || cp->tp.world > 1 || !(i == 0 ? ph.nt == 2 : cp->o_nt2)))
+      return -10;
     const int max_rows = (cp->seq == 0 && cp->attn_g == 0 && !f8) ? 16 : 4;
     if (p.M < 1 || p.M > max_rows || p.K % 128 != 0 || p.N % (16 * ph.nt) != 0) return -10;
     const size_t xrows = ((size_t)p.M * (p.K + 8) * 2 + 15) & ~(size_t)15;
@@ -1801,8 +1937,24 @@ extern "C" int vwa_chain_prepare(ChainParams* cp, int grid) {
 }
 
 extern "C" int vwa_chain_launch(const ChainParams* d_cp, int seq, int n_phases, int attn_g, int lds, int grid,
-                                hipStream_t st, int xg2, int f8, int o2, int n_layers) {
+                                hipStream_t st, int xg2, int f8, int o2, int n_layers, int pk) {
   if (attn_g) lds = lds > (int)MqLds<128, 8>::bytes ? lds : (int)MqLds<128, 8>::bytes;
+  if (pk) {  // packed bf16 weights (SkinnyParams::w_pack): Llama tail with attention, o_proj in 32-column tiles
+    if (seq != 0 || f8 || xg2 || !o2 || (attn_g != 4 && attn_g != 8) || (n_phases != 3 && n_phases != 4)) return -10;
+    if (n_layers > 1 && n_phases != 4) return -10;
+#define VWA_CHAIN_LAUNCH_PK(N, G, MULTI_) \
+  hipLaunchKernelGGL((chain_kernel<8, 0, N, G, 0, false, false, true, false, MULTI_, true>), dim3(grid), dim3(8 * 64), lds, \
+                     st, d_cp, n_layers)
+    if (n_layers > 1) {
+      if (attn_g == 4) VWA_CHAIN_LAUNCH_PK(4, 4, true); else VWA_CHAIN_LAUNCH_PK(4, 8, true);
+    } else if (n_phases == 4) {
+      if (attn_g == 4) VWA_CHAIN_LAUNCH_PK(4, 4, false); else VWA_CHAIN_LAUNCH_PK(4, 8, false);
+    } else {
+      if (attn_g == 4) VWA_CHAIN_LAUNCH_PK(3, 4, false); else VWA_CHAIN_LAUNCH_PK(3, 8, false);
+    }
+#undef VWA_CHAIN_LAUNCH_PK
+    return (int)hipGetLastError();
+  }
   if (n_layers > 1) {  // one launch over n_layers consecutive Llama tails (chain_kernel MULTI)
     if (seq != 0 || n_phases != 4 || xg2 || (attn_g != 4 && attn_g != 8) || (!f8 && !o2) || (f8 && o2)) return -10;
 #define VWA_CHAIN_LAUNCH_MULTI(G, F8_, O2_) \

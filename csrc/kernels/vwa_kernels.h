@@ -37,6 +37,17 @@ struct SkinnyParams {
   // of some row are computed, the other outputs are left unwritten (the sampler never reads a
   // masked logit).  Ignored (every tile computed) where the kernel cannot take it.
   const uint32_t* col_mask; int col_mask_ld; int col_mask_rows;
+  // w_pack (chained decode layer, bf16 tiled weights, ops.pack_weight): the same weights as W in a
+  // lossless 13-bit form, one 3328-byte block per (16-row tile T, k-group kg) in W's block order:
+  //   [0, 2048)     the low byte of every bf16 (exponent bit 0 + mantissa): two 1 KB loads, lane l's
+  //                 16 bytes at + 16 l = fragments s = 2 h, 2 h + 1 of load h (8 bytes each)
+  //   [2048, 3072)  4-bit codes of the high byte's exponent part (bf16 bits 14..8): lane l's dword
+  //                 s holds fragment s -- nibble 2 i: element i, nibble 2 i + 1: element 4 + i
+  //   [3072, 3328)  sign bits, one dword per lane: bit 8 i + 2 s + q = sign of element 4 q + i
+  // high byte = sign << 7 | (w_pack_base + code).  A block holding a value whose bits 14..8 lie
+  // outside [w_pack_base, w_pack_base + 15] has w_pack_flag[T * (K / 128) + kg] != 0 and is read
+  // from W instead, so every bf16 bit pattern is reproduced.  Null: W is streamed as it is.
+  const uint8_t* w_pack; const uint8_t* w_pack_flag; int w_pack_base;
 };
 
 // Paged / strided KV addressing shared by the attention kernels:
@@ -103,7 +114,7 @@ struct ChainTP {
 };
 
 // (64-byte aligned: a multi-layer launch indexes an array of them, and each one's scalar-cache
-// warm-up, chain_kernel, covers exactly its 25 lines)
+// warm-up, chain_kernel, covers exactly its 26 lines)
 struct alignas(64) ChainParams {
   ChainPhase ph[kChainMaxPhases];
   int n;
@@ -258,7 +269,7 @@ int vwa_chain_prepare(ChainParams* cp, int grid);
 // n_layers > 1: d_cp is an array of n_layers descriptors of consecutive 4-phase Llama tails with the
 // attention phase, run by ONE launch (skinny_stream.hip chain_kernel MULTI)
 int vwa_chain_launch(const ChainParams* d_cp, int seq, int n_phases, int attn_g, int lds, int grid, hipStream_t st,
-                     int xg2 = 0, int f8 = 0, int o2 = 0, int n_layers = 1);
+                     int xg2 = 0, int f8 = 0, int o2 = 0, int n_layers = 1, int pk = 0);
 // -10: a shape / role table the kernel does not take (the caller keeps per-kernel launches)
 int vwa_wdec_launch(const WdecParams* p, int grid, hipStream_t st);
 int vwa_gemm(int epi, const GemmParams* p, hipStream_t st);

@@ -35,6 +35,8 @@ def main():
     ap.add_argument("--row-major", dest="tiled", action="store_false",
                     help="row-major [N, K] weights instead of the pre-tiled layout (ops.tile_weight)")
     ap.add_argument("--fp8", action="store_true", help="fp8 tiled weights (the W8A16 chain, ops.FP8Weight)")
+    ap.add_argument("--pack", action="store_true",
+                    help="(--attn, tiled bf16) the chained launches stream the packed 13-bit weights (ops.pack_weight)")
     ap.add_argument("--no-plan", action="store_true",
                     help="(--attn) every launch derives the attention partition itself (no step plan)")
     ap.add_argument("--no-stamps", action="store_true",
@@ -104,6 +106,12 @@ def main():
         for w in Ws:
             w.update({k + "_t": ops.tile_weight(w[k]) for k in ("o", "gu", "down", "qkv")})
     wt = (lambda w, k: w[k + "_t"]) if a.tiled else (lambda w, k: w[k])  # noqa: E731
+    if a.pack:
+        assert a.attn and a.tiled and not a.fp8, "--pack: the attention launch over tiled bf16 weights"
+        for w, sc in zip(Ws, sck):
+            pk = {k: ops.pack_weight(w[k + "_t"]) for k in ("o", "gu", "down", "qkv")}
+            w["pk"] = pk  # (the descriptors hold raw pointers)
+            sc.update({"p_" + k: pk[k].data for k in pk}, p_base=[pk[k].base for k in ("o", "gu", "down", "qkv")])
     plan = {}
     if a.attn and not a.no_plan:  # layers 1.. of a step: the plan layer 0 wrote (written once below)
         plan = dict(a_plan=torch.zeros(1024 * 16, dtype=torch.int32, device=dev), a_plan_mode=2)
@@ -198,7 +206,8 @@ def main():
             col = col[col > 0]
             if col.numel():
                 extra[nm] = [round(float((col.median() - t0) * 10e-3), 2), round(float((col.max() - t0) * 10e-3), 2)]
-    r = dict(kernel="chain_probe", rows=M, plan=bool(plan), fp8=a.fp8, ctx=a.ctx if a.attn else None, warm_kv=a.warm_kv, n_splits=a.n_splits, kv_tok_major=a.kv_tok_major, bar_mode=a.bar_mode, tiled=a.tiled, row_table=a.row_table, separate_us=round(t_sep, 2), chained_us=round(t_ch, 2),
+    r = dict(kernel="chain_probe", rows=M, plan=bool(plan), fp8=a.fp8, pack=a.pack,
+             pack_flagged=sum(p_.n_flagged for w in Ws for p_ in w.get("pk", {}).values()), ctx=a.ctx if a.attn else None, warm_kv=a.warm_kv, n_splits=a.n_splits, kv_tok_major=a.kv_tok_major, bar_mode=a.bar_mode, tiled=a.tiled, row_table=a.row_table, separate_us=round(t_sep, 2), chained_us=round(t_ch, 2),
              stamps_med_us=[round(x, 2) for x in med], stamps_min_us=[round(x, 2) for x in mn],
              stamps_max_us=[round(x, 2) for x in mx],
              legend=("start,end_attn," if a.attn else "start,") + "end_o,wait_o,end_gu,wait_gu,end_down,wait_down,end_qkv")

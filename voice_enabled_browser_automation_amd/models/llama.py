@@ -95,6 +95,15 @@ class LlamaModel:
         for L in self.layers:
             L.qkv, L.o, L.gu, L.down = T(L.qkv), T(L.o), T(L.gu), T(L.down)
         self.lm_head = T(self.lm_head)
+        # VWA_CHAIN_PACK: the chained decode layer streams a lossless 13-bit form of its weights
+        # (ops.pack_weight, 0.81 x the bytes) next to the tiled copy, which stays for prefill, steps of
+        # more than 4 rows, the per-kernel path and the flagged blocks.  Only where the chained launch
+        # that decodes it exists: one rank, head_dim 128, GQA group 4 or 8.
+        if (self.tp.size == 1 and self.hd == 128 and self.nq // self.nkv in (4, 8) and ops.env_flag("VWA_CHAIN_PACK")
+                and ops.native_available()):
+            for L in self.layers:
+                for w in (L.qkv, L.o, L.gu, L.down):
+                    w.pk = ops.pack_weight(w.t)
         torch.cuda.empty_cache()
 
     def _quantize_fp8(self) -> None:
@@ -114,6 +123,7 @@ class LlamaModel:
         ts = [self.lm_head] + [t for L in self.layers for t in (L.qkv, L.o, L.gu, L.down)]
         n = sum(t.numel() * t.element_size() for t in ts) + self.embed.numel() * self.embed.element_size()
         n += sum(t.scale.numel() * 4 for t in ts if isinstance(t, ops.FP8Weight))
+        n += sum(t.pk.data.numel() for t in ts if getattr(t, "pk", None) is not None)  # (VWA_CHAIN_PACK)
         return n
 
     # ------------------------------------------------------------------ weights
@@ -323,7 +333,16 @@ class LlamaModel:
         sc = {}
         if f8:  # W8A16 chain: fp8 tiled weights converted to bf16 in registers, per-row scales in the epilogues
             sc = dict(s_o=L.o.scale, s_gu=L.gu.scale, s_down=L.down.scale, s_qkv=N.qkv.scale if nxt else None)
+        # packed weights (VWA_CHAIN_PACK, _tile_weights): only the launch with the attention phase decodes them
+        ws = [L.o, L.gu, L.down] + ([N.qkv] if nxt else [])
+        pk = {}
+        if tiled and not f8 and all(getattr(w, "pk", None) is not None for w in ws) and ops.env_flag("VWA_CHAIN_PACK"):
+            pk = dict(p_o=L.o.pk.data, p_gu=L.gu.pk.data, p_down=L.down.pk.data, p_qkv=N.qkv.pk.data if nxt else None,
+                      p_base=[w.pk.base for w in ws])
+
         def make(a):
+            if a:
+                a = dict(a, **pk)
             return ops.ext().chain_make(
                 bufs.hidden[:M], bufs.attn[:M], bufs.act[:M], wsel(L.o), wsel(L.gu), wsel(L.down), self.cfg.rms_eps,
                 wsel(N.qkv) if nxt else None, self.nq, self.nkv, self.hd,

@@ -257,10 +257,11 @@ class TiledWeight:
     the model keeps one copy of each weight.  ``dense()`` rebuilds the row-major matrix for the
     CPU reference and diagnostics."""
 
-    __slots__ = ("t",)
+    __slots__ = ("t", "pk")
 
-    def __init__(self, w: Optional[torch.Tensor] = None, t: Optional[torch.Tensor] = None):
+    def __init__(self, w: Optional[torch.Tensor] = None, t: Optional[torch.Tensor] = None, pk=None):
         self.t = tile_weight(w) if t is None else t
+        self.pk = pk  # optional PackedWeight of the same weight (the chained decode layer streams it)
 
     def dense(self) -> torch.Tensor:
         return untile_weight(self.t)
@@ -288,7 +289,106 @@ class TiledWeight:
         return self.t.element_size()
 
     def to(self, device) -> "TiledWeight":
-        return TiledWeight(t=self.t.to(device))
+        return TiledWeight(t=self.t.to(device), pk=None if self.pk is None else self.pk.to(device))
+
+
+# ----------------------------------------------------------------------------- packed bf16 weights
+# Lossless 13-bit form of a tiled bf16 weight for the chained decode layer (vwa_kernels.h
+# SkinnyParams::w_pack).  A bf16 is [sign | 8 exponent bits | 7 mantissa bits]; its low byte
+# (exponent bit 0 + mantissa) is kept as it is, its sign goes to a bit plane, and bits 14..8 -- the
+# exponent without its lowest bit, which spans only a few values in a weight matrix -- become a
+# 4-bit code relative to a per-tensor base: 8 + 4 + 1 = 13 bits.  A (16-row tile, 128-wide k-group)
+# block holding a value outside the base's 16-value window (32 binades) is flagged and read from
+# the bf16 copy by the kernel, so every bit pattern is reproduced.
+PACK_BLOCK = 3328   # bytes per packed block: 2048 low bytes | 1024 code nibbles | 256 sign bits
+PACK_WINDOW = 16    # values of (bits >> 8) & 0x7F a tensor's codes cover: base .. base + 15
+
+
+class PackedWeight:
+    """``data``: uint8 [blocks * 3328 | blocks] -- the packed blocks in tile_weight's block order,
+    then one flag byte per block (non-zero: read the block from the bf16 copy); ``base``: the
+    tensor's exponent base; ``n_flagged``: flagged blocks."""
+
+    __slots__ = ("data", "base", "blocks", "n_flagged")
+
+    def __init__(self, data: torch.Tensor, base: int, blocks: int, n_flagged: int):
+        self.data, self.base, self.blocks, self.n_flagged = data, base, blocks, n_flagged
+
+    @property
+    def flags(self) -> torch.Tensor:
+        return self.data[self.blocks * PACK_BLOCK:]
+
+    def to(self, device) -> "PackedWeight":
+        return PackedWeight(self.data.to(device), self.base, self.blocks, self.n_flagged)
+
+
+def _pack_bits(t: torch.Tensor) -> torch.Tensor:
+    """bf16 bits of a tiled weight as int32 [blocks, s = 4, lane = 64, e = 8]."""
+    return (t.contiguous().view(torch.int16).reshape(-1, 4, 64, 8).to(torch.int32)) & 0xFFFF
+
+
+def pack_base(t: torch.Tensor) -> int:
+    """The exponent base of a tensor: its largest finite value's bits 14..8, less the window."""
+    v = _pack_bits(t)
+    hi7 = (v >> 8) & 0x7F
+    finite = ((v >> 7) & 0xFF) != 0xFF
+    top = int(torch.where(finite, hi7, torch.zeros_like(hi7)).max().item()) if v.numel() else 0
+    return max(0, top - (PACK_WINDOW - 1))
+
+
+def pack_weight(t: torch.Tensor, *, verify: bool = True, chunk: int = 4096) -> PackedWeight:
+    """Pack a tiled bf16 weight (tile_weight's [N, K]).  ``verify``: unpack every block with the
+    kernel's arithmetic (unpack_weight) and compare the bits, flagged blocks excluded."""
+    assert t.dtype == torch.bfloat16 and t.dim() == 2 and t.shape[0] % 16 == 0 and t.shape[1] % 128 == 0
+    blocks = t.numel() // 2048
+    base = pack_base(t)
+    data = torch.empty(blocks * (PACK_BLOCK + 1), dtype=torch.uint8, device=t.device)
+    body, flags = data[:blocks * PACK_BLOCK].view(blocks, PACK_BLOCK), data[blocks * PACK_BLOCK:]
+    tb = t.contiguous().view(-1, 2048)
+    for b0 in range(0, blocks, chunk):  # (chunks bound the int32 temporaries)
+        v = _pack_bits(tb[b0:b0 + chunk])                     # [n, s, lane, e]
+        n = v.shape[0]
+        code = ((v >> 8) & 0x7F) - base
+        bad = (code < 0) | (code >= PACK_WINDOW)
+        flags[b0:b0 + n] = bad.reshape(n, -1).any(dim=1).to(torch.uint8)
+        code = code.clamp(0, PACK_WINDOW - 1)
+        out = body[b0:b0 + n]
+        # low bytes: load h = s >> 1 gives lane l the 8 bytes of fragment 2 h, then of 2 h + 1
+        out[:, :2048] = (v & 0xFF).reshape(n, 2, 2, 64, 8).permute(0, 1, 3, 2, 4).reshape(n, 2048).to(torch.uint8)
+        # codes: lane l's dword s, byte i = code of element i | code of element 4 + i << 4
+        c = code.reshape(n, 4, 64, 2, 4)
+        out[:, 2048:3072] = (c[:, :, :, 0] | (c[:, :, :, 1] << 4)).permute(0, 2, 1, 3).reshape(n, 1024).to(torch.uint8)
+        # signs: lane l's dword, bit 8 i + 2 s + q = sign of fragment s's element 4 q + i
+        sg = (v >> 15).reshape(n, 4, 64, 2, 4)                # [n, s, lane, q, i]
+        sh = (2 * torch.arange(4, device=t.device).view(1, 4, 1, 1, 1) + torch.arange(2, device=t.device).view(1, 1, 1, 2, 1))
+        out[:, 3072:] = (sg << sh).sum(dim=(1, 3)).reshape(n, 256).to(torch.uint8)
+    pw = PackedWeight(data, base, blocks, int(flags.sum().item()) if blocks else 0)
+    if verify:
+        back = unpack_weight(pw, t.shape)
+        ok = (back.view(torch.int16).view(-1, 2048) == tb.view(torch.int16)).all(dim=1) | (flags != 0)
+        if not bool(ok.all()):
+            raise RuntimeError("pack_weight: a packed block does not decode to its bf16 bits")
+    return pw
+
+
+def unpack_weight(pw: PackedWeight, shape, *, chunk: int = 4096) -> torch.Tensor:
+    """The tiled bf16 weight a PackedWeight decodes to, with the kernel's arithmetic
+    (skinny_stream.hip pack_decode); flagged blocks decode to whatever their clamped codes give."""
+    dev = pw.data.device
+    body = pw.data[:pw.blocks * PACK_BLOCK].view(pw.blocks, PACK_BLOCK)
+    out = torch.empty(pw.blocks, 2048, dtype=torch.int16, device=dev)
+    for b0 in range(0, pw.blocks, chunk):
+        blk = body[b0:b0 + chunk].to(torch.int32)
+        n = blk.shape[0]
+        lo = blk[:, :2048].reshape(n, 2, 64, 2, 8).permute(0, 1, 3, 2, 4).reshape(n, 4, 64, 8)   # [n, s, lane, e]
+        nb = blk[:, 2048:3072].reshape(n, 64, 4, 4).permute(0, 2, 1, 3)                          # [n, s, lane, i]
+        code = torch.stack([nb & 0xF, nb >> 4], dim=3).reshape(n, 4, 64, 8)                      # e = 4 q + i
+        sb = blk[:, 3072:].reshape(n, 1, 64, 1, 4)                                               # byte i of the lane's dword
+        sh = (2 * torch.arange(4, device=dev).view(1, 4, 1, 1, 1) + torch.arange(2, device=dev).view(1, 1, 1, 2, 1))
+        sg = ((sb >> sh) & 1).reshape(n, 4, 64, 8)
+        v = lo | ((code + pw.base) << 8) | (sg << 15)
+        out[b0:b0 + n] = (((v.reshape(n, 2048) & 0xFFFF) ^ 0x8000) - 0x8000).to(torch.int16)
+    return out.view(torch.bfloat16).view(shape)
 
 
 def _stream_ok(x: torch.Tensor, w) -> bool:
