@@ -1,48 +1,20 @@
-// PyTorch bindings of the word-alignment kernel library (_vwa_align.so).
-//
-// Same rules as csrc/bindings.cpp: every entry point validates device, dtype, contiguity, shape and
-// range on the host BEFORE launching (a bad shape must never reach a kernel), names the offending
-// argument, and launches on the current HIP stream of the anchor tensor's device under a device
-// guard.  The few checks needed are a copy of that file's vocabulary.
-#include <torch/extension.h>
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
-#include <c10/core/DeviceGuard.h>
-
+// PyTorch bindings of the word-alignment kernel library (_vwa_align.so).  Rules and check vocabulary:
+// csrc/torch_checks.h.
+#include "torch_checks.h"
 #include "align/align.h"
 
 namespace {
 
-using at::Tensor;
-using OptTensor = c10::optional<Tensor>;
+using namespace vwa::checks;
 constexpr auto kBF16 = at::kBFloat16;
 
-hipStream_t cur_stream(const Tensor& t) {
-  return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream();
-}
-bool aligned(const Tensor& t, uintptr_t bytes) {
-  return (reinterpret_cast<uintptr_t>(t.data_ptr()) & (bytes - 1)) == 0;
-}
-// GPU tensor: on the anchor's device, with the dtype the kernel reads
-void check_gpu(const Tensor& t, const Tensor& a, at::ScalarType dt, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
-  TORCH_CHECK(t.device() == a.device(), name, " must be on ", a.device(), " (the device this call launches on), not ",
-              t.device());
-  TORCH_CHECK(t.scalar_type() == dt, name, " must be ", dt, ", not ", t.scalar_type());
-}
-// Vector: contiguous GPU tensor of >= n elements
-void check_vec(const Tensor& t, const Tensor& a, at::ScalarType dt, int64_t n, const char* name) {
-  check_gpu(t, a, dt, name);
-  TORCH_CHECK(t.is_contiguous() && t.numel() >= n, name, " must be contiguous with >= ", n, " elements, not ",
-              t.sizes());
-}
-// f32 matrix (last two dims of t) with unit inner stride and non-overlapping rows
-void check_f32_rows(const Tensor& t, const Tensor& a, int64_t dims, const char* name) {
+// f32 [planes, rows, cols] with unit inner stride, rows and planes that do not overlap
+void check_planes(const Tensor& t, const Tensor& a, const char* name) {
   check_gpu(t, a, at::kFloat, name);
-  TORCH_CHECK(t.dim() == dims && t.stride(dims - 1) == 1 && t.stride(dims - 2) >= t.size(dims - 1), name, " must be ",
-              dims, "-D with contiguous rows");
-  TORCH_CHECK(dims < 3 || t.stride(0) >= t.size(1) * t.stride(1), name, " planes must not overlap");
+  TORCH_CHECK(t.dim() == 3 && t.stride(2) == 1 && t.stride(1) >= t.size(2), name,
+              " must be 3-D with contiguous rows");
+  TORCH_CHECK(t.stride(0) >= t.size(1) * t.stride(1), name, " planes must not overlap");
 }
-void check_rc(int rc, const char* what) { TORCH_CHECK(rc == 0, what, " launch failed with code ", rc); }
 
 void attn_probs(const Tensor& q, const Tensor& k, const Tensor& heads, int64_t n_keys, double scale, const Tensor& out) {
   check_gpu(q, q, kBF16, "q");
@@ -57,7 +29,7 @@ void attn_probs(const Tensor& q, const Tensor& k, const Tensor& heads, int64_t n
   check_vec(heads, q, at::kInt, 1, "heads");
   TORCH_CHECK(heads.dim() == 1 && heads.numel() <= 65535, "heads must be 1-D with 1..65535 entries");
   TORCH_CHECK(n_keys >= 1 && n_keys <= S, "n_keys must be in [1, S_max = ", S, "], not ", n_keys);
-  check_f32_rows(out, q, 3, "out");
+  check_planes(out, q, "out");
   TORCH_CHECK(out.size(0) == heads.numel() && out.size(1) == T && out.size(2) == S, "out must be [n_sel, T, S_max] = [",
               heads.numel(), ", ", T, ", ", S, "], not ", out.sizes());
   const c10::DeviceGuard guard(q.device());
@@ -69,13 +41,13 @@ void attn_probs(const Tensor& q, const Tensor& k, const Tensor& heads, int64_t n
 }
 
 void align_cost(const Tensor& probs, int64_t n_tokens, int64_t n_keys, const Tensor& out) {
-  check_f32_rows(probs, probs, 3, "probs");
+  check_planes(probs, probs, "probs");
   const int64_t Hs = probs.size(0), T = probs.size(1), S = probs.size(2);
   TORCH_CHECK(Hs >= 1 && Hs < (1 << 20), "probs: the head count must be in [1, 2^20), not ", Hs);
   TORCH_CHECK(n_tokens >= 1 && n_tokens <= T, "n_tokens must be in [1, T = ", T, "], not ", n_tokens);
   TORCH_CHECK(n_keys >= 1 && n_keys <= S, "n_keys must be in [1, S_max = ", S, "], not ", n_keys);
   TORCH_CHECK(S < (1 << 24), "probs: S_max too large");
-  check_f32_rows(out, probs, 2, "out");
+  check_mat(out, probs, at::kFloat, 0, 0, "out");
   TORCH_CHECK(out.size(0) == T && out.size(1) == S, "out must be [T, S_max] = [", T, ", ", S, "], not ", out.sizes());
   const c10::DeviceGuard guard(probs.device());
   check_rc(vwa_align_cost(probs.data_ptr<float>(), probs.stride(0), probs.stride(1), (int)Hs, (int)n_tokens,
@@ -85,7 +57,7 @@ void align_cost(const Tensor& probs, int64_t n_tokens, int64_t n_keys, const Ten
 
 void dtw_path(const Tensor& cost, int64_t n_tokens, int64_t n_keys, const Tensor& first_frame,
               const Tensor& last_frame, const OptTensor& workspace) {
-  check_f32_rows(cost, cost, 2, "cost");
+  check_mat(cost, cost, at::kFloat, 0, 0, "cost");
   const int64_t T = cost.size(0), S = cost.size(1);
   TORCH_CHECK(n_tokens >= 1 && n_tokens <= T && n_tokens <= kDtwMaxRows, "n_tokens must be in [1, min(T = ", T, ", ",
               kDtwMaxRows, ")], not ", n_tokens);
@@ -109,21 +81,13 @@ void dtw_path(const Tensor& cost, int64_t n_tokens, int64_t n_keys, const Tensor
 
 void token_logprob(const Tensor& logits, const Tensor& targets, const OptTensor& mask, int64_t vocab,
                    const Tensor& out) {
-  check_f32_rows(logits, logits, 2, "logits");
+  check_mat(logits, logits, at::kFloat, 0, 0, "logits");
   const int64_t N = logits.size(0);
   TORCH_CHECK(N >= 1 && N < (1 << 24), "logits: the row count must be in [1, 2^24), not ", N);
   TORCH_CHECK(vocab >= 1 && vocab <= logits.size(1), "vocab must be in [1, ", logits.size(1), "], not ", vocab);
   check_vec(targets, logits, at::kInt, N, "targets");
-  int64_t mask_stride = 0;
-  if (mask.has_value()) {
-    const Tensor& m = *mask;
-    check_gpu(m, logits, at::kInt, "mask");
-    TORCH_CHECK(m.dim() == 2 && m.stride(1) == 1 && (m.size(0) == N || m.size(0) == 1) && m.stride(0) >= 0,
-                "mask must be [N or 1, words] with contiguous rows");
-    TORCH_CHECK(m.size(1) * 32 >= vocab, "mask has ", m.size(1), " words: fewer than vocab = ", vocab, " bits");
-    mask_stride = m.size(0) == 1 ? 0 : m.stride(0);
-    TORCH_CHECK(m.size(0) == 1 || mask_stride >= m.size(1) || mask_stride == 0, "mask rows must not overlap");
-  }
+  // ([N, words] may be one row expanded: stride 0)
+  const int64_t mask_stride = mask.has_value() ? check_mask(*mask, logits, N, vocab, true, true) : 0;
   check_vec(out, logits, at::kFloat, N, "out");
   const c10::DeviceGuard guard(logits.device());
   check_rc(vwa_token_logprob(logits.data_ptr<float>(), logits.stride(0), (int)N, (int)vocab, targets.data_ptr<int>(),

@@ -4,7 +4,7 @@
 // One workgroup per row, two sweeps of the (L2-resident) row: the maximum, then the sum of
 // exp(x - max); out = (x_target - max) - log(sum).  A row whose only allowed id is the target
 // gives exactly 0 (sum = exp(0) = 1).  A row with no allowed id gives NaN.
-#include "kernels/common.h"
+#include "kernels/logit_row.h"
 #include "align/align.h"
 
 using namespace vwa;
@@ -12,8 +12,6 @@ using namespace vwa;
 namespace {
 
 constexpr int kThreads = 256;
-
-VWA_DEVICE bool allowed(const uint32_t* mask, int v) { return !mask || ((mask[v >> 5] >> (v & 31)) & 1u); }
 
 __global__ __launch_bounds__(kThreads) void token_logprob_kernel(const float* __restrict__ logits, int64_t ld,
                                                                  int vocab, const int* __restrict__ targets,
@@ -29,7 +27,7 @@ __global__ __launch_bounds__(kThreads) void token_logprob_kernel(const float* __
   m = wave_max(m);
   if (lane == 0) red[wave] = m;
   __syncthreads();
-  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  m = wg_max(red);
   __syncthreads();
   float s = 0.f;
   for (int v = threadIdx.x; v < vocab; v += kThreads)
@@ -38,7 +36,7 @@ __global__ __launch_bounds__(kThreads) void token_logprob_kernel(const float* __
   if (lane == 0) red[wave] = s;
   __syncthreads();
   if (threadIdx.x == 0) {
-    s = (red[0] + red[1]) + (red[2] + red[3]);
+    s = (red[0] + red[1]) + (red[2] + red[3]);  // (wg_sum4's order, written out: see the comment there)
     const int t = min(max(targets[row], 0), vocab - 1);
     // (a log-probability: rounding may not lift it above 0; a masked-out target stays -inf)
     out[row] = allowed(mk, t) ? fminf((x[t] - m) - logf(s), 0.f) : -INFINITY;

@@ -14,7 +14,7 @@
 // A row can give the group no more than its own K best and a tile the row no more than its own K
 // best, so nothing is lost.  Ties are compared on the f32 scores themselves: two logits whose
 // scores round to the same f32 are ordered by their ids, as the contract says.
-#include "kernels/common.h"
+#include "kernels/logit_row.h"
 #include "beam/beam.h"
 
 using namespace vwa;
@@ -27,7 +27,6 @@ constexpr int kPer = kBeamTile / kThreads;  // columns a lane holds
 constexpr int kList = 2 * kBeamMaxWidth;    // entries of a (row, tile) list
 constexpr int kNoKey = 0x7fffffff;
 
-VWA_DEVICE bool allowed(const uint32_t* mask, int v) { return !mask || ((mask[v >> 5] >> (v & 31)) & 1u); }
 VWA_DEVICE bool finite(float v) { return fabsf(v) < INFINITY; }  // (false for a NaN)
 
 // (score, key) pairs: the better one has the higher score, among equal scores the lower key
@@ -88,7 +87,7 @@ __global__ __launch_bounds__(kThreads) void lse_part_kernel(const float* __restr
   m = wave_max(m);
   if (lane == 0) red[0][wave] = m;
   __syncthreads();
-  m = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+  m = wg_max(red[0]);
   float s = 0.f;
   if (m > -INFINITY) {
 #pragma unroll
@@ -99,7 +98,7 @@ __global__ __launch_bounds__(kThreads) void lse_part_kernel(const float* __restr
   __syncthreads();
   if (threadIdx.x == 0) {
     part_m[row * T + tile] = m;
-    part_s[row * T + tile] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    part_s[row * T + tile] = wg_sum4(red[1]);
   }
 }
 

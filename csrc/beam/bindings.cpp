@@ -1,44 +1,12 @@
-// PyTorch bindings of the beam search library (_vwa_beam.so).
-//
-// Same rules as csrc/bindings.cpp, csrc/align/bindings.cpp and csrc/sot/bindings.cpp: the entry
-// point validates device, dtype, contiguity, shape and range on the host BEFORE launching (a bad
-// shape must never reach a kernel), names the offending argument, and launches on the current HIP
-// stream of the anchor tensor's device under a device guard.  The few checks needed are a copy of
-// those files' vocabulary.
-#include <torch/extension.h>
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
-#include <c10/core/DeviceGuard.h>
-
+// PyTorch bindings of the beam search library (_vwa_beam.so).  Rules and check vocabulary:
+// csrc/torch_checks.h.
+#include "torch_checks.h"
 #include "beam/beam.h"
 
 namespace {
 
-using at::Tensor;
-using OptTensor = c10::optional<Tensor>;
+using namespace vwa::checks;
 
-hipStream_t cur_stream(const Tensor& t) {
-  return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream();
-}
-// GPU tensor: on the anchor's device, with the dtype the kernel reads
-void check_gpu(const Tensor& t, const Tensor& a, at::ScalarType dt, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
-  TORCH_CHECK(t.device() == a.device(), name, " must be on ", a.device(), " (the device this call launches on), not ",
-              t.device());
-  TORCH_CHECK(t.scalar_type() == dt, name, " must be ", dt, ", not ", t.scalar_type());
-}
-// Vector: contiguous GPU tensor of >= n elements
-void check_vec(const Tensor& t, const Tensor& a, at::ScalarType dt, int64_t n, const char* name) {
-  check_gpu(t, a, dt, name);
-  TORCH_CHECK(t.is_contiguous() && t.numel() >= n, name, " must be contiguous with >= ", n, " elements, not ",
-              t.sizes());
-}
-// Matrix with unit inner stride and non-overlapping rows, >= rows x >= cols
-void check_rows(const Tensor& t, const Tensor& a, at::ScalarType dt, int64_t rows, int64_t cols, const char* name) {
-  check_gpu(t, a, dt, name);
-  TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1 && t.stride(0) >= t.size(1), name, " must be 2-D with contiguous rows");
-  TORCH_CHECK(t.size(0) >= rows && t.size(1) >= cols, name, " must be [>= ", rows, ", >= ", cols, "], not ",
-              t.sizes());
-}
 // int32 [G, W], contiguous
 void check_gw(const Tensor& t, const Tensor& a, int64_t G, int64_t W, const char* name) {
   check_gpu(t, a, at::kInt, name);
@@ -49,7 +17,6 @@ void check_width(int64_t G, int64_t W) {
   TORCH_CHECK(W >= 2 && W <= kBeamMaxWidth, "W (beams per group) must be in [2, ", kBeamMaxWidth, "], not ", W);
   TORCH_CHECK(G >= 1 && G * W <= kBeamMaxRows, "G x W must be in [1, ", kBeamMaxRows, "] rows, not ", G, " x ", W);
 }
-void check_rc(int rc, const char* what) { TORCH_CHECK(rc == 0, what, " launch failed with code ", rc); }
 
 int64_t beam_select_workspace(int64_t rows, int64_t vocab) {
   TORCH_CHECK(rows >= 1 && rows <= kBeamMaxRows, "rows must be in [1, ", kBeamMaxRows, "], not ", rows);
@@ -59,9 +26,7 @@ int64_t beam_select_workspace(int64_t rows, int64_t vocab) {
 
 void beam_select(const Tensor& logits, const Tensor& cum, const OptTensor& mask, int64_t vocab, int64_t W,
                  const Tensor& cand_score, const Tensor& cand_beam, const Tensor& cand_tok, const Tensor& workspace) {
-  check_gpu(logits, logits, at::kFloat, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1),
-              "logits must be 2-D with contiguous rows");
+  check_mat(logits, logits, at::kFloat, 0, 0, "logits");
   const int64_t N = logits.size(0);
   TORCH_CHECK(W >= 2 && W <= kBeamMaxWidth, "W (beams per group) must be in [2, ", kBeamMaxWidth, "], not ", W);
   TORCH_CHECK(N >= W && N % W == 0, "logits: ", N, " rows are not groups of W = ", W);
@@ -70,20 +35,11 @@ void beam_select(const Tensor& logits, const Tensor& cum, const OptTensor& mask,
   TORCH_CHECK(vocab >= 1 && vocab <= logits.size(1) && vocab <= kBeamMaxVocab, "vocab must be in [1, min(",
               logits.size(1), " (the logits' row length), ", kBeamMaxVocab, ")], not ", vocab);
   check_vec(cum, logits, at::kFloat, N, "cum");
-  int64_t mask_stride = 0;
-  if (mask.has_value()) {
-    const Tensor& m = *mask;
-    check_gpu(m, logits, at::kInt, "mask");
-    TORCH_CHECK(m.dim() == 2 && m.stride(1) == 1 && (m.size(0) == N || m.size(0) == 1) && m.stride(0) >= 0,
-                "mask must be [N or 1, words] with contiguous rows");
-    TORCH_CHECK(m.size(1) * 32 >= vocab, "mask has ", m.size(1), " words: fewer than vocab = ", vocab, " bits");
-    mask_stride = m.size(0) == 1 ? 0 : m.stride(0);
-    TORCH_CHECK(m.size(0) == 1 || mask_stride >= m.size(1), "mask rows must not overlap");
-  }
+  const int64_t mask_stride = mask.has_value() ? check_mask(*mask, logits, N, vocab, true, false) : 0;
   const int64_t K = 2 * W;
-  check_rows(cand_score, logits, at::kFloat, G, K, "cand_score");
-  check_rows(cand_beam, logits, at::kInt, G, K, "cand_beam");
-  check_rows(cand_tok, logits, at::kInt, G, K, "cand_tok");
+  check_mat(cand_score, logits, at::kFloat, G, K, "cand_score");
+  check_mat(cand_beam, logits, at::kInt, G, K, "cand_beam");
+  check_mat(cand_tok, logits, at::kInt, G, K, "cand_tok");
   const int64_t ldc = cand_score.stride(0);
   TORCH_CHECK(cand_beam.stride(0) == ldc && cand_tok.stride(0) == ldc,
               "cand_score, cand_beam and cand_tok must have one row stride");
@@ -114,18 +70,15 @@ void kv_beam_gather(const Tensor& k_cache, const Tensor& v_cache, const Tensor& 
   TORCH_CHECK((bs * hd * 2) % 16 == 0, "k_cache: a head's block (bs x hd = ", bs, " x ", hd,
               " bf16) must be a multiple of 16 bytes");
   TORCH_CHECK(H * bs * hd * 2 / 16 <= (1 << 24), "k_cache: a block is too large");
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(k_cache.data_ptr()) | reinterpret_cast<uintptr_t>(v_cache.data_ptr())) % 16 == 0,
-              "k_cache and v_cache must be 16-byte aligned");
+  TORCH_CHECK(aligned(k_cache, 16) && aligned(v_cache, 16), "k_cache and v_cache must be 16-byte aligned");
   TORCH_CHECK(slots.dim() == 2, "slots must be [G, W], not ", slots.sizes());
   const int64_t G = slots.size(0), W = slots.size(1);
   check_width(G, W);
   check_gw(slots, k_cache, G, W, "slots");
   check_gw(parents, k_cache, G, W, "parents");
   check_vec(n_ctx, k_cache, at::kInt, G, "n_ctx");
-  check_gpu(block_table, k_cache, at::kInt, "block_table");
-  TORCH_CHECK(block_table.dim() == 2 && block_table.stride(1) == 1 && block_table.stride(0) >= block_table.size(1) &&
-                  block_table.size(0) >= 1 && block_table.size(0) < (1 << 24) && block_table.size(1) >= 1,
-              "block_table must be [sessions, blocks per session] with contiguous rows");
+  check_mat(block_table, k_cache, at::kInt, 1, 1, "block_table");
+  TORCH_CHECK(block_table.size(0) < (1 << 24), "block_table: too many sessions, ", block_table.size(0));
   const int64_t bps = block_table.size(1);
   TORCH_CHECK(max_ctx >= 0 && max_ctx <= bps * bs, "max_ctx = ", max_ctx, " exceeds the block table's ", bps,
               " blocks of ", bs, " positions");

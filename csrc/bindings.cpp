@@ -1,34 +1,21 @@
 // PyTorch bindings for the gfx950 kernel library.
 //
-// Every entry point validates shapes/dtypes/devices on the host BEFORE launching (a bad
-// shape must never reach a kernel: an out-of-bounds access can reset the whole node), then
-// launches on the current HIP stream of the tensor's device -- so each op is capturable in a
+// The rules every entry point follows, and the check vocabulary shared with the small libraries'
+// bindings (check_gpu / check_vec / check_mat / ...), are in torch_checks.h; the checks only this
+// library needs (check_gpu_or_pinned / check_rows / check_slots / check_cache / check_qkv) are below.
+// Each op launches on the current HIP stream of its anchor's device, so it is capturable in a
 // torch.cuda.CUDAGraph (= hipGraph on ROCm).
-//
-// Every tensor whose pointer goes into a params struct or a launcher argument passes through the
-// check vocabulary below (check_gpu / check_gpu_or_pinned / check_rows / check_vec); a new entry
-// point reads as the list of what it requires.
 #include <mutex>
 #include <string>
 
-#include <torch/extension.h>
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
-#include <c10/core/DeviceGuard.h>
-
+#include "torch_checks.h"
 #include "kernels/vwa_kernels.h"
 
 namespace {
 
-using at::Tensor;
-using OptTensor = c10::optional<Tensor>;
+using namespace vwa::checks;
 constexpr auto kBF16 = at::kBFloat16;
 constexpr auto kF8 = at::kFloat8_e4m3fn;
-
-// torch-ROCm exposes GPUs as device type "cuda"; the masquerading accessor returns the stream
-// torch itself launches on (including the capture stream inside torch.cuda.graph).
-hipStream_t cur_stream(const Tensor& t) {
-  return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream();
-}
 
 const uint16_t* bfp(const Tensor& t) { return reinterpret_cast<const uint16_t*>(t.data_ptr()); }
 uint16_t* bfp_mut(const Tensor& t) { return reinterpret_cast<uint16_t*>(t.data_ptr()); }
@@ -37,21 +24,9 @@ uint16_t* bfp_mut_opt(const OptTensor& t) { return t.has_value() ? bfp_mut(*t) :
 template <class T>
 T* ptr_opt(const OptTensor& t) { return t.has_value() ? t->data_ptr<T>() : nullptr; }
 unsigned long long* u64p(const Tensor& t) { return reinterpret_cast<unsigned long long*>(t.data_ptr<int64_t>()); }
-bool aligned(const Tensor& t, uintptr_t bytes) {
-  return (reinterpret_cast<uintptr_t>(t.data_ptr()) & (bytes - 1)) == 0;
-}
 
-// ---- check vocabulary.  `a` is the entry point's anchor: the tensor given to DeviceGuard and
-// cur_stream (checked against itself).  `name` is the argument's Python keyword name.
-void check_anchor(const Tensor& a, const char* name) { TORCH_CHECK(a.is_cuda(), name, " must be a GPU tensor"); }
-// GPU tensor: on the anchor's device, with the dtype the kernel reads
-void check_gpu(const Tensor& t, const Tensor& a, at::ScalarType dt, const char* name) {
-  check_anchor(t, name);
-  TORCH_CHECK(t.device() == a.device(), name, " must be on ", a.device(), " (the device this call launches on), not ",
-              t.device());
-  TORCH_CHECK(t.scalar_type() == dt, name, " must be ", dt, ", not ", t.scalar_type());
-}
-// ... or pinned host memory (zero-copy grammar masks, token readback)
+// ---- the checks only this library needs (the shared ones: torch_checks.h)
+// GPU tensor or pinned host memory (zero-copy grammar masks, token readback)
 void check_gpu_or_pinned(const Tensor& t, const Tensor& a, at::ScalarType dt, const char* name) {
   if (t.is_cuda()) return check_gpu(t, a, dt, name);
   TORCH_CHECK(t.is_pinned(), name, " must be a GPU or pinned host tensor");
@@ -72,12 +47,6 @@ void check_rows(const Tensor& t, const char* name) {
 void check_sizes(const Tensor& t, std::initializer_list<int64_t> want, const char* name) {
   TORCH_CHECK(t.sizes() == at::IntArrayRef(want), name, " must be ", at::IntArrayRef(want), ", not ", t.sizes());
 }
-// Vector: contiguous GPU tensor of >= n (exact: == n) elements
-void check_vec(const Tensor& t, const Tensor& a, at::ScalarType dt, int64_t n, const char* name, bool exact = false) {
-  check_gpu(t, a, dt, name);
-  TORCH_CHECK(t.is_contiguous() && (exact ? t.numel() == n : t.numel() >= n), name, " must be contiguous with ",
-              exact ? "" : ">= ", n, " elements, not ", t.sizes());
-}
 // Tensor lists (wdec_run): (index, dtype, minimum length) of each slot
 struct Slot { int i; at::ScalarType dt; int64_t n; };
 void check_slots(const std::vector<Tensor>& v, const Tensor& a, const char* list, std::initializer_list<Slot> slots) {
@@ -90,7 +59,6 @@ void check_cache(const Tensor& c, const Tensor& a, const char* name) {
   TORCH_CHECK(c.dim() == 4 && c.stride(3) == 1 && c.stride(0) > 0 && c.stride(1) > 0 && c.stride(2) > 0, name,
               " must be [blocks, kv_heads, block_size, head_dim] with contiguous head_dim rows");
 }
-void check_rc(int rc, const char* what) { TORCH_CHECK(rc == 0, what, " launch failed with code ", rc); }
 
 int device_cus(const Tensor& t) {
   static int cached[64] = {0};

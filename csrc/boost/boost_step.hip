@@ -6,6 +6,7 @@
 // strictly within a list, and a root edge is skipped when the state's list holds its token, so no
 // two lanes add to one column.
 #include "boost/boost.h"
+#include "kernels/common.h"
 
 namespace {
 
@@ -88,8 +89,6 @@ __global__ __launch_bounds__(kThreads) void boost_step_kernel(
   }
 }
 
-bool overlap(const int* a, const int* b, int n) { return a < b + n && b < a + n; }
-
 }  // namespace
 
 extern "C" int vwa_boost_step(float* logits, int64_t ld, int rows, int vocab, const int* edge_off, const int* edge_tok,
@@ -103,8 +102,8 @@ extern "C" int vwa_boost_step(float* logits, int64_t ld, int rows, int vocab, co
   if (S < 1 || S > kBoostMaxStates || E < 1 || E > kBoostMaxEdges) return -4;
   if (parents) {
     if (W < 1 || W > rows || rows % W) return -5;
-    if (overlap(state_in, state_out, rows)) return -6;
-  } else if (state_in != state_out && overlap(state_in, state_out, rows)) {
+    if (vwa::overlap(state_in, 4 * (int64_t)rows, state_out, 4 * (int64_t)rows)) return -6;
+  } else if (state_in != state_out && vwa::overlap(state_in, 4 * (int64_t)rows, state_out, 4 * (int64_t)rows)) {
     return -6;  // (the same buffer steps in place; a shifted overlap would read other rows' new states)
   }
   hipLaunchKernelGGL(boost_step_kernel, dim3(rows), dim3(kThreads), 0, st, logits, ld, vocab, edge_off, edge_tok,

@@ -171,4 +171,12 @@ VWA_DEVICE int xcd_remap(int bid, int nwg) {
   return base + i;
 }
 
+// Host side, for the launchers' own argument checks: do the byte ranges [p, p + n) and [q, q + m)
+// overlap?
+inline bool overlap(const void* p, int64_t n, const void* q, int64_t m) {
+  const char* a = static_cast<const char*>(p);
+  const char* b = static_cast<const char*>(q);
+  return a < b + m && b < a + n;
+}
+
 }  // namespace vwa

@@ -1,70 +1,37 @@
-// PyTorch bindings of the transcript score library (_vwa_score.so).
-//
-// Same rules as csrc/bindings.cpp and the align / sot / beam / boost / tsrules bindings: the entry
-// point validates device, dtype, contiguity, shape and range on the host BEFORE launching (a bad
-// shape must never reach a kernel), names the offending argument, and launches on the current HIP
-// stream of the anchor tensor's device under a device guard.  The few checks needed are a copy of
-// those files' vocabulary.
-#include <torch/extension.h>
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
-#include <c10/core/DeviceGuard.h>
-
+// PyTorch bindings of the transcript score library (_vwa_score.so).  Rules and check vocabulary:
+// csrc/torch_checks.h.
+#include "torch_checks.h"
 #include "score/score.h"
 
 namespace {
 
-using at::Tensor;
-using OptTensor = c10::optional<Tensor>;
+using namespace vwa::checks;
 
-hipStream_t cur_stream(const Tensor& t) {
-  return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream();
-}
-// GPU tensor: on the anchor's device, with the dtype the kernel reads
-void check_gpu(const Tensor& t, const Tensor& a, at::ScalarType dt, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
-  TORCH_CHECK(t.device() == a.device(), name, " must be on ", a.device(), " (the device this call launches on), not ",
-              t.device());
-  TORCH_CHECK(t.scalar_type() == dt, name, " must be ", dt, ", not ", t.scalar_type());
-}
-// contiguous 1-D [>= rows]
-void check_vec(const Tensor& t, const Tensor& a, at::ScalarType dt, int64_t rows, const char* name) {
-  check_gpu(t, a, dt, name);
-  TORCH_CHECK(t.dim() == 1 && t.is_contiguous() && t.numel() >= rows, name, " must be contiguous 1-D with >= ", rows,
-              " elements, not ", t.sizes());
-}
 // Counts: contiguous [>= rows, 2] int32
 void check_cnt(const Tensor& t, const Tensor& a, int64_t rows, const char* name) {
   check_gpu(t, a, at::kInt, name);
   TORCH_CHECK(t.dim() == 2 && t.size(1) == 2 && t.is_contiguous() && t.size(0) >= rows, name,
               " must be contiguous [>= ", rows, ", 2], not ", t.sizes());
 }
-void check_rc(int rc, const char* what) { TORCH_CHECK(rc == 0, what, " launch failed with code ", rc); }
 
 void score_step(const Tensor& logits, int64_t vocab, int64_t eot, const Tensor& mask, const Tensor& enable,
                 const Tensor& tokens, const Tensor& sum_in, const Tensor& sum_out, const Tensor& cnt_in,
                 const Tensor& cnt_out, const OptTensor& step_lp) {
-  check_gpu(logits, logits, at::kFloat, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1),
-              "logits must be 2-D with contiguous rows");
-  check_gpu(enable, logits, at::kInt, "enable");
-  TORCH_CHECK(enable.dim() == 1 && enable.is_contiguous(), "enable must be contiguous 1-D, not ", enable.sizes());
+  check_mat(logits, logits, at::kFloat, 0, 0, "logits");
+  check_vec_1d(enable, logits, at::kInt, 0, "enable");
   const int64_t rows = enable.numel();
   TORCH_CHECK(rows >= 1 && rows <= kScoreMaxRows, "enable: rows must be in [1, ", kScoreMaxRows, "], not ", rows);
   TORCH_CHECK(logits.size(0) >= rows, "logits must have >= ", rows, " rows (one per enable), not ", logits.size(0));
   TORCH_CHECK(vocab >= 1 && vocab <= logits.size(1) && vocab <= kScoreMaxVocab, "vocab must be in [1, min(",
               logits.size(1), " (the logits' row length), ", kScoreMaxVocab, ")], not ", vocab);
   TORCH_CHECK(eot >= 0 && eot < vocab, "eot must be in [0, vocab = ", vocab, "), not ", eot);
-  check_gpu(mask, logits, at::kInt, "mask");
-  const int64_t words = (vocab + 31) / 32;
-  TORCH_CHECK(mask.dim() == 2 && mask.stride(1) == 1 && mask.size(1) >= words &&
-                  (mask.size(0) == 1 || (mask.size(0) >= rows && mask.stride(0) >= mask.size(1))),
-              "mask must be [1 or >= ", rows, ", >= ", words, "] with contiguous rows, not ", mask.sizes());
-  check_vec(tokens, logits, at::kInt, rows, "tokens");
-  check_vec(sum_in, logits, at::kFloat, rows, "sum_in");
-  check_vec(sum_out, logits, at::kFloat, rows, "sum_out");
+  const int64_t mask_stride = check_mask(mask, logits, rows, vocab, false, false);
+  check_vec_1d(tokens, logits, at::kInt, rows, "tokens");
+  check_vec_1d(sum_in, logits, at::kFloat, rows, "sum_in");
+  check_vec_1d(sum_out, logits, at::kFloat, rows, "sum_out");
   check_cnt(cnt_in, logits, rows, "cnt_in");
   check_cnt(cnt_out, logits, rows, "cnt_out");
-  if (step_lp.has_value()) check_vec(*step_lp, logits, at::kFloat, rows, "step_lp");
+  if (step_lp.has_value()) check_vec_1d(*step_lp, logits, at::kFloat, rows, "step_lp");
   // the in-place pairs may coincide exactly; nothing else among the state tensors and step_lp may overlap
   struct Span { const char* name; const char* p; int64_t n; };
   const Span sp[5] = {{"sum_in", (const char*)sum_in.data_ptr(), 4 * rows},
@@ -76,12 +43,12 @@ void score_step(const Tensor& logits, int64_t vocab, int64_t eot, const Tensor& 
     for (int j = i + 1; j < 5; ++j) {
       if (!sp[i].p || !sp[j].p) continue;
       if (sp[i].p == sp[j].p && ((i == 0 && j == 1) || (i == 2 && j == 3))) continue;
-      TORCH_CHECK(!(sp[i].p < sp[j].p + sp[j].n && sp[j].p < sp[i].p + sp[i].n), sp[j].name, " must not overlap ",
+      TORCH_CHECK(!overlaps(sp[i].p, sp[i].n, sp[j].p, sp[j].n), sp[j].name, " must not overlap ",
                   sp[i].name, " (sum_out may be sum_in itself and cnt_out may be cnt_in itself, nothing else)");
     }
   const c10::DeviceGuard guard(logits.device());
   check_rc(vwa_score_step(logits.data_ptr<float>(), logits.stride(0), (int)rows, (int)vocab, (int)eot,
-                          mask.data_ptr<int>(), mask.size(0) == 1 ? 0 : mask.stride(0), enable.data_ptr<int>(),
+                          mask.data_ptr<int>(), mask_stride, enable.data_ptr<int>(),
                           tokens.data_ptr<int>(), sum_in.data_ptr<float>(), sum_out.data_ptr<float>(),
                           cnt_in.data_ptr<int>(), cnt_out.data_ptr<int>(),
                           step_lp.has_value() ? step_lp->data_ptr<float>() : nullptr, cur_stream(logits)),

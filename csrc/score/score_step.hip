@@ -7,51 +7,17 @@
 // lane's scaled once to the common maximum.  Every order is fixed, so a launch repeats its bits.
 // Every thread reads the row's state cells before the first barrier and thread 0 writes them after
 // the second: with sum_out == sum_in and cnt_out == cnt_in no wave reads a cell already written.
+#include "kernels/logit_row.h"
 #include "score/score.h"
 
 #include <math.h>
+
+using namespace vwa;
 
 namespace {
 
 constexpr int kThreads = 512;
 constexpr int kWaves = kThreads / 64;
-
-__device__ __forceinline__ float neg_inf() { return -__builtin_huge_valf(); }
-
-__device__ __forceinline__ bool allowed(const uint32_t* __restrict__ m, int c) { return (m[c >> 5] >> (c & 31)) & 1u; }
-
-// the allow-bits of columns c .. c + 3 (c + 3 < vocab)
-__device__ __forceinline__ uint32_t allowed4(const uint32_t* __restrict__ m, int c) {
-  const int w = c >> 5, w3 = (c + 3) >> 5;
-  uint64_t bits = m[w];
-  if (w3 != w) bits |= (uint64_t)m[w3] << 32;
-  return (uint32_t)(bits >> (c & 31)) & 0xFu;
-}
-
-// Columns [0, n) of row x shared among the workgroup's threads: one(c) for the columns before the
-// first 16-byte aligned address and after the last whole float4, four(c) for the float4 at c between.
-template <class F1, class F4>
-__device__ __forceinline__ void sweep(const float* x, int n, int tid, F1 one, F4 four) {
-  int head = (int)(((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2);
-  if (head > n) head = n;
-  const int nvec = (n - head) >> 2;
-  const int tail = head + (nvec << 2);
-  if (tid < head) one(tid);
-  for (int i = tid; i < nvec; i += kThreads) four(head + (i << 2));
-  if (tid < n - tail) one(tail + tid);
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(kThreads) void score_step_kernel(
     const float* __restrict__ logits, int64_t ld, int vocab, int eot, const int* __restrict__ mask, int64_t mask_ld,
@@ -81,52 +47,29 @@ __global__ __launch_bounds__(kThreads) void score_step_kernel(
   const uint32_t* mrow = reinterpret_cast<const uint32_t*>(mask) + (int64_t)r * mask_ld;
   const float ninf = neg_inf();
   float m = ninf, s = 0.f;
-  auto lse = [&](float v) {
-    if (v > m) {
-      s = s * expf(m - v) + 1.f;
-      m = v;
-    } else if (v > ninf) {
-      s += expf(v - m);
-    }
-  };
-  sweep(x, vocab, tid, [&](int c) { if (allowed(mrow, c)) lse(x[c]); },
-        [&](int c) {
-          const float4 v = *reinterpret_cast<const float4*>(x + c);
-          const uint32_t k = allowed4(mrow, c);
-          if (k & 1u) lse(v.x);
-          if (k & 2u) lse(v.y);
-          if (k & 4u) lse(v.z);
-          if (k & 8u) lse(v.w);
-        });
+  OnlineLse acc{m, s, ninf};
+  sweep<kThreads>(x, 0, vocab, tid, [&](int c) { if (allowed<true>(mrow, c)) acc.add(x[c]); },
+                  [&](int c) { acc.add4(*reinterpret_cast<const float4*>(x + c), allowed4(mrow, c)); });
 
   const int wave = tid >> 6, lane = tid & 63;
   const float wm = wave_max(m);
   if (lane == 0) sh_m[wave] = wm;
   __syncthreads();
-  float bm = ninf;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) bm = fmaxf(bm, sh_m[w]);
-  const float ws = wave_sum(s > 0.f ? s * expf(m - bm) : 0.f);
+  const float bm = wg_max(sh_m);
+  const float ws = wave_sum(acc.scaled(bm));
   if (lane == 0) sh_s[wave] = ws;
   __syncthreads();
   if (tid != 0) return;
   float S = 0.f;
 #pragma unroll
   for (int w = 0; w < kWaves; ++w) S += sh_s[w];
-  const float xt = allowed(mrow, tok) ? x[tok] : ninf;  // (tok < vocab: tested above)
+  const float xt = allowed<true>(mrow, tok) ? x[tok] : ninf;  // (tok < vocab: tested above)
   float lp = ninf;
   if (xt > ninf && S > 0.f) lp = fminf(xt - (bm + logf(S)), 0.f);
   sum_out[r] = sum0 + lp;
   cnt_out[2 * r] = n0 + 1;
   cnt_out[2 * r + 1] = tok == eot ? 1 : 0;
   if (step_lp) step_lp[r] = lp;
-}
-
-// byte ranges [a, a + na) and [b, b + nb)
-bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-  const char* p = static_cast<const char*>(a);
-  const char* q = static_cast<const char*>(b);
-  return p < q + nb && q < p + na;
 }
 
 }  // namespace

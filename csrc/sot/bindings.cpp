@@ -1,49 +1,18 @@
-// PyTorch bindings of the start-of-transcript probe library (_vwa_sot.so).
-//
-// Same rules as csrc/bindings.cpp and csrc/align/bindings.cpp: the entry point validates device,
-// dtype, contiguity, shape and range on the host BEFORE launching (a bad shape must never reach a
-// kernel), names the offending argument, and launches on the current HIP stream of the anchor
-// tensor's device under a device guard.  The few checks needed are a copy of those files' vocabulary.
-#include <torch/extension.h>
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
-#include <c10/core/DeviceGuard.h>
-
+// PyTorch bindings of the start-of-transcript probe library (_vwa_sot.so).  Rules and check vocabulary:
+// csrc/torch_checks.h.
 #include <vector>
 
+#include "torch_checks.h"
 #include "sot/sot.h"
 
 namespace {
 
-using at::Tensor;
-using OptTensor = c10::optional<Tensor>;
-
-hipStream_t cur_stream(const Tensor& t) {
-  return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream();
-}
-// GPU tensor: on the anchor's device, with the dtype the kernel reads
-void check_gpu(const Tensor& t, const Tensor& a, at::ScalarType dt, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
-  TORCH_CHECK(t.device() == a.device(), name, " must be on ", a.device(), " (the device this call launches on), not ",
-              t.device());
-  TORCH_CHECK(t.scalar_type() == dt, name, " must be ", dt, ", not ", t.scalar_type());
-}
-// Vector: contiguous GPU tensor of >= n elements
-void check_vec(const Tensor& t, const Tensor& a, at::ScalarType dt, int64_t n, const char* name) {
-  check_gpu(t, a, dt, name);
-  TORCH_CHECK(t.is_contiguous() && t.numel() >= n, name, " must be contiguous with >= ", n, " elements, not ",
-              t.sizes());
-}
-// f32 matrix with unit inner stride and non-overlapping rows
-void check_f32_rows(const Tensor& t, const Tensor& a, const char* name) {
-  check_gpu(t, a, at::kFloat, name);
-  TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1 && t.stride(0) >= t.size(1), name, " must be 2-D with contiguous rows");
-}
-void check_rc(int rc, const char* what) { TORCH_CHECK(rc == 0, what, " launch failed with code ", rc); }
+using namespace vwa::checks;
 
 void sot_probe(const Tensor& logits, int64_t vocab, int64_t lang0, int64_t n_lang, const std::vector<int64_t>& allow,
                int64_t no_speech_id, const Tensor& lang_probs, const Tensor& lang_tok, const Tensor& lang_conf,
                const Tensor& no_speech, const OptTensor& tok_dst, const OptTensor& dst_rows) {
-  check_f32_rows(logits, logits, "logits");
+  check_mat(logits, logits, at::kFloat, 0, 0, "logits");
   const int64_t rows = logits.size(0);
   TORCH_CHECK(rows >= 1 && rows < (1 << 24), "logits: the row count must be in [1, 2^24), not ", rows);
   TORCH_CHECK(vocab >= 1 && vocab <= logits.size(1) && vocab < (int64_t(1) << 31), "vocab must be in [1, ",
@@ -62,9 +31,7 @@ void sot_probe(const Tensor& logits, int64_t vocab, int64_t lang0, int64_t n_lan
     for (int b = 0; b < 32; ++b) any = any || (((words[i] >> b) & 1u) && 32 * i + b < n_lang);
   }
   TORCH_CHECK(any, "allow admits no language below n_lang = ", n_lang);
-  check_f32_rows(lang_probs, logits, "lang_probs");
-  TORCH_CHECK(lang_probs.size(0) >= rows && lang_probs.size(1) >= n_lang, "lang_probs must be [>= ", rows, ", >= ",
-              n_lang, "], not ", lang_probs.sizes());
+  check_mat(lang_probs, logits, at::kFloat, rows, n_lang, "lang_probs");
   check_vec(lang_tok, logits, at::kInt, rows, "lang_tok");
   check_vec(lang_conf, logits, at::kFloat, rows, "lang_conf");
   check_vec(no_speech, logits, at::kFloat, rows, "no_speech");

@@ -6,7 +6,7 @@
 // does.  The language part is one lane per language (n_lang <= 128): the maximum over the allowed
 // ids, the lowest lane holding it (compared on the raw logits, so ties resolve exactly), the sum of
 // exp(x - max) and each lane's own probability.
-#include "kernels/common.h"
+#include "kernels/logit_row.h"
 #include "sot/sot.h"
 
 using namespace vwa;
@@ -53,8 +53,8 @@ __global__ __launch_bounds__(kThreads) void sot_probe_kernel(const float* __rest
     redi[0][wave] = low_w;
   }
   __syncthreads();
-  m = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
-  const float ml = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+  m = wg_max(red[0]);
+  const float ml = wg_max(red[1]);
   const int low = min(min(redi[0][0], redi[0][1]), min(redi[0][2], redi[0][3]));  // lowest allowed language
 
   float s = 0.f;
@@ -70,8 +70,8 @@ __global__ __launch_bounds__(kThreads) void sot_probe_kernel(const float* __rest
     redi[1][wave] = best_w;
   }
   __syncthreads();
-  s = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
-  const float sl = (red[3][0] + red[3][1]) + (red[3][2] + red[3][3]);
+  s = wg_sum4(red[2]);
+  const float sl = wg_sum4(red[3]);
   int best = min(min(redi[1][0], redi[1][1]), min(redi[1][2], redi[1][3]));
   if (best == kNone) best = low;  // no logit of A equals the maximum (all NaN): still an id of A
 

@@ -9,58 +9,28 @@
 // Nothing is written before the second reduction's barrier, so no lane reads a column another has
 // banned, and the state goes out after the first barrier: with state_out == state_in every wave has
 // read the row's cells by then.
+#include "kernels/logit_row.h"
 #include "tsrules/tsrules.h"
 
 #include <math.h>
+
+using namespace vwa;
 
 namespace {
 
 constexpr int kThreads = 512;
 constexpr int kWaves = kThreads / 64;
 
-__device__ __forceinline__ float neg_inf() { return -__builtin_huge_valf(); }
-
-__device__ __forceinline__ bool allowed(const uint32_t* __restrict__ m, int c) { return (m[c >> 5] >> (c & 31)) & 1u; }
-
-// the allow-bits of columns c .. c + 3 (c + 3 < vocab)
-__device__ __forceinline__ uint32_t allowed4(const uint32_t* __restrict__ m, int c) {
-  const int w = c >> 5, w3 = (c + 3) >> 5;
-  uint64_t bits = m[w];
-  if (w3 != w) bits |= (uint64_t)m[w3] << 32;
-  return (uint32_t)(bits >> (c & 31)) & 0xFu;
-}
-
-// Columns [lo, hi) of row x shared among the workgroup's threads: one(c) for the columns before the
-// first 16-byte aligned address and after the last whole float4, four(c) for the float4 at c between.
+// sweep() of [lo, hi); the rules often leave a range empty, which then costs one uniform branch
 template <class F1, class F4>
-__device__ __forceinline__ void sweep(const float* x, int lo, int hi, int tid, F1 one, F4 four) {
-  if (lo >= hi) return;
-  int head = (int)(((16u - (unsigned)((uintptr_t)(x + lo) & 15u)) & 15u) >> 2);
-  if (head > hi - lo) head = hi - lo;
-  const int body = lo + head;
-  const int nvec = (hi - body) >> 2;
-  const int tail = body + (nvec << 2);
-  if (tid < head) one(lo + tid);
-  for (int i = tid; i < nvec; i += kThreads) four(body + (i << 2));
-  if (tid < hi - tail) one(tail + tid);
+VWA_DEVICE void sweep_range(const float* x, int lo, int hi, int tid, F1 one, F4 four) {
+  if (lo < hi) sweep<kThreads>(x, lo, hi, tid, one, four);
 }
 
-__device__ __forceinline__ void ban(float* x, int lo, int hi, int tid) {
+VWA_DEVICE void ban(float* x, int lo, int hi, int tid) {
   const float ninf = neg_inf();
-  sweep(x, lo, hi, tid, [&](int c) { x[c] = ninf; },
-        [&](int c) { *reinterpret_cast<float4*>(x + c) = make_float4(ninf, ninf, ninf, ninf); });
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+  sweep_range(x, lo, hi, tid, [&](int c) { x[c] = ninf; },
+              [&](int c) { *reinterpret_cast<float4*>(x + c) = make_float4(ninf, ninf, ninf, ninf); });
 }
 
 __global__ __launch_bounds__(kThreads) void ts_rules_kernel(
@@ -112,43 +82,27 @@ __global__ __launch_bounds__(kThreads) void ts_rules_kernel(
   const uint32_t* mrow = reinterpret_cast<const uint32_t*>(mask) + (int64_t)r * mask_ld;
   const float ninf = neg_inf();
   float M = ninf;
-  sweep(x, tx_lo, tx_hi, tid, [&](int c) { if (allowed(mrow, c)) M = fmaxf(M, x[c]); },
-        [&](int c) {
-          const float4 v = *reinterpret_cast<const float4*>(x + c);
-          const uint32_t k = allowed4(mrow, c);
-          if (k & 1u) M = fmaxf(M, v.x);
-          if (k & 2u) M = fmaxf(M, v.y);
-          if (k & 4u) M = fmaxf(M, v.z);
-          if (k & 8u) M = fmaxf(M, v.w);
-        });
+  sweep_range(x, tx_lo, tx_hi, tid, [&](int c) { if (allowed<true>(mrow, c)) M = fmaxf(M, x[c]); },
+              [&](int c) {
+                const float4 v = *reinterpret_cast<const float4*>(x + c);
+                const uint32_t k = allowed4(mrow, c);
+                if (k & 1u) M = fmaxf(M, v.x);
+                if (k & 2u) M = fmaxf(M, v.y);
+                if (k & 4u) M = fmaxf(M, v.z);
+                if (k & 8u) M = fmaxf(M, v.w);
+              });
   float m = ninf, s = 0.f;
-  auto lse = [&](float v) {
-    if (v > m) {
-      s = s * expf(m - v) + 1.f;
-      m = v;
-    } else if (v > ninf) {
-      s += expf(v - m);
-    }
-  };
-  sweep(x, ts_begin + a, ts_begin + b, tid, [&](int c) { if (allowed(mrow, c)) lse(x[c]); },
-        [&](int c) {
-          const float4 v = *reinterpret_cast<const float4*>(x + c);
-          const uint32_t k = allowed4(mrow, c);
-          if (k & 1u) lse(v.x);
-          if (k & 2u) lse(v.y);
-          if (k & 4u) lse(v.z);
-          if (k & 8u) lse(v.w);
-        });
+  OnlineLse acc{m, s, ninf};
+  sweep_range(x, ts_begin + a, ts_begin + b, tid, [&](int c) { if (allowed<true>(mrow, c)) acc.add(x[c]); },
+              [&](int c) { acc.add4(*reinterpret_cast<const float4*>(x + c), allowed4(mrow, c)); });
 
   const int wave = tid >> 6, lane = tid & 63;
   const float wM = wave_max(M), wm = wave_max(m);
   if (lane == 0) { sh_M[wave] = wM; sh_m[wave] = wm; }
   __syncthreads();
   if (tid == 0) { so[0] = n; so[1] = last; so[2] = prev; so[3] = last_ts; }
-  float bM = ninf, bm = ninf;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) { bM = fmaxf(bM, sh_M[w]); bm = fmaxf(bm, sh_m[w]); }
-  const float ws = wave_sum(s > 0.f ? s * expf(m - bm) : 0.f);
+  const float bM = wg_max(sh_M), bm = wg_max(sh_m);
+  const float ws = wave_sum(acc.scaled(bm));
   if (lane == 0) sh_s[wave] = ws;
   __syncthreads();
   float S = 0.f;
@@ -167,8 +121,6 @@ __global__ __launch_bounds__(kThreads) void ts_rules_kernel(
   ban(x, ts_begin + b, vocab, tid);
 }
 
-bool overlap(const int* a, const int* b, int64_t n) { return a < b + n && b < a + n; }
-
 }  // namespace
 
 extern "C" int vwa_ts_rules_step(float* logits, int64_t ld, int rows, int vocab, int eot, int ts_begin,
@@ -179,7 +131,7 @@ extern "C" int vwa_ts_rules_step(float* logits, int64_t ld, int rows, int vocab,
   if (vocab < 1 || vocab > kTsMaxVocab || ld < vocab) return -3;
   if (eot < 0 || eot >= ts_begin || ts_begin >= vocab) return -4;
   if (mask_ld != 0 && mask_ld < (vocab + 31) / 32) return -5;
-  if (state_in != state_out && overlap(state_in, state_out, 4 * (int64_t)rows)) return -6;
+  if (state_in != state_out && overlap(state_in, 16 * (int64_t)rows, state_out, 16 * (int64_t)rows)) return -6;
   hipLaunchKernelGGL(ts_rules_kernel, dim3(rows), dim3(kThreads), 0, st, logits, ld, vocab, eot, ts_begin, max_initial,
                      mask, mask_ld, enable, state_in, state_out, tokens);
   return (int)hipGetLastError();

@@ -18,6 +18,7 @@ Layout conventions shared by kernels, reference and models:
 """
 from __future__ import annotations
 
+import importlib
 import math
 from typing import Dict, Optional, Tuple
 
@@ -80,6 +81,28 @@ def native_available() -> bool:
         return True
     except RuntimeError:
         return False
+
+_LIBS: dict = {}  # module name -> the loaded small kernel library, or the error of its first load
+
+
+def _load_lib(module_name: str, noun: str):
+    """A small kernel library of this package (csrc/<dir> -> ``<module_name>.so``), loaded once: a
+    failed load is remembered and reported again, never retried."""
+    lib = _LIBS.get(module_name)
+    if isinstance(lib, BaseException):
+        raise RuntimeError(f"native gfx950 {noun} library unavailable: {lib}") from lib
+    if lib is None:
+        try:
+            lib = importlib.import_module("." + module_name, __name__)
+        except BaseException as e:  # noqa: BLE001
+            _LIBS[module_name] = e
+            raise RuntimeError(
+                f"native gfx950 {noun} library {module_name}.so failed to load; build it with "
+                "`python -m voice_enabled_browser_automation_amd.ops.build`"
+            ) from e
+        _LIBS[module_name] = lib
+    return lib
+
 
 
 def _gpu(t: torch.Tensor) -> bool:
@@ -1247,30 +1270,13 @@ def conv1d_gelu(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], *, 
 
 
 # ----------------------------------------------------------------------------- word alignment
-_ALIGN = None
-_ALIGN_ERR: Optional[BaseException] = None
 DTW_MAX_ROWS = 448       # csrc/align/align.h kDtwMaxRows: one lane per token row
 DTW_LDS_TRACE = 48 * 1024  # cells whose step trace the DTW kernel keeps in LDS
 
 
 def align_ext():
-    """Load the word-alignment kernel library ``_vwa_align.so`` (once). Raises if unavailable."""
-    global _ALIGN, _ALIGN_ERR
-    if _ALIGN is not None:
-        return _ALIGN
-    if _ALIGN_ERR is not None:
-        raise RuntimeError(f"native gfx950 alignment library unavailable: {_ALIGN_ERR}") from _ALIGN_ERR
-    try:
-        from . import _vwa_align as m  # type: ignore
-
-        _ALIGN = m
-        return m
-    except BaseException as e:  # noqa: BLE001
-        _ALIGN_ERR = e
-        raise RuntimeError(
-            "native gfx950 alignment library _vwa_align.so failed to load; build it with "
-            "`python -m voice_enabled_browser_automation_amd.ops.build`"
-        ) from e
+    """The word-alignment kernel library ``_vwa_align.so`` (loaded once). Raises if unavailable."""
+    return _load_lib("_vwa_align", "alignment")
 
 
 def attn_probs(q: torch.Tensor, k: torch.Tensor, heads, n_keys: int, scale: float, out: torch.Tensor) -> torch.Tensor:
@@ -1365,29 +1371,12 @@ def env_int(name: str) -> int:
 
 
 # ----------------------------------------------------------------------------- start-of-transcript probe
-_SOT = None
-_SOT_ERR: Optional[BaseException] = None
 SOT_MAX_LANGS = 128  # csrc/sot/sot.h kSotMaxLangs: one lane per language
 
 
 def sot_ext():
-    """Load the start-of-transcript probe library ``_vwa_sot.so`` (once). Raises if unavailable."""
-    global _SOT, _SOT_ERR
-    if _SOT is not None:
-        return _SOT
-    if _SOT_ERR is not None:
-        raise RuntimeError(f"native gfx950 SOT probe library unavailable: {_SOT_ERR}") from _SOT_ERR
-    try:
-        from . import _vwa_sot as m  # type: ignore
-
-        _SOT = m
-        return m
-    except BaseException as e:  # noqa: BLE001
-        _SOT_ERR = e
-        raise RuntimeError(
-            "native gfx950 SOT probe library _vwa_sot.so failed to load; build it with "
-            "`python -m voice_enabled_browser_automation_amd.ops.build`"
-        ) from e
+    """The start-of-transcript probe library ``_vwa_sot.so`` (loaded once). Raises if unavailable."""
+    return _load_lib("_vwa_sot", "SOT probe")
 
 
 def sot_probe(logits: torch.Tensor, vocab: int, lang0: int, n_lang: int, no_speech_id: int,
@@ -1445,31 +1434,14 @@ def sot_probe(logits: torch.Tensor, vocab: int, lang0: int, n_lang: int, no_spee
 
 
 # ----------------------------------------------------------------------------- beam search
-_BEAM = None
-_BEAM_ERR: Optional[BaseException] = None
 BEAM_MAX_WIDTH = 8        # csrc/beam/beam.h kBeamMaxWidth
 BEAM_MAX_ROWS = 64        # ... kBeamMaxRows: groups x beams per launch
 BEAM_MAX_VOCAB = 1 << 20  # ... kBeamMaxVocab
 
 
 def beam_ext():
-    """Load the beam search library ``_vwa_beam.so`` (once). Raises if unavailable."""
-    global _BEAM, _BEAM_ERR
-    if _BEAM is not None:
-        return _BEAM
-    if _BEAM_ERR is not None:
-        raise RuntimeError(f"native gfx950 beam search library unavailable: {_BEAM_ERR}") from _BEAM_ERR
-    try:
-        from . import _vwa_beam as m  # type: ignore
-
-        _BEAM = m
-        return m
-    except BaseException as e:  # noqa: BLE001
-        _BEAM_ERR = e
-        raise RuntimeError(
-            "native gfx950 beam search library _vwa_beam.so failed to load; build it with "
-            "`python -m voice_enabled_browser_automation_amd.ops.build`"
-        ) from e
+    """The beam search library ``_vwa_beam.so`` (loaded once). Raises if unavailable."""
+    return _load_lib("_vwa_beam", "beam search")
 
 
 def _beam_width(what: str, rows: int, W: int) -> int:
@@ -1589,8 +1561,6 @@ def kv_beam_gather(k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: to
 
 
 # ----------------------------------------------------------------------------- keyterm boosting
-_BOOST = None
-_BOOST_ERR: Optional[BaseException] = None
 BOOST_MAX_ROWS = 64          # csrc/boost/boost.h kBoostMaxRows: rows per launch
 BOOST_MAX_STATES = 1 << 20   # ... kBoostMaxStates
 BOOST_MAX_EDGES = 1 << 24    # ... kBoostMaxEdges
@@ -1602,23 +1572,8 @@ BOOST_CAP_EDGES = 65536
 
 
 def boost_ext():
-    """Load the keyterm boosting library ``_vwa_boost.so`` (once). Raises if unavailable."""
-    global _BOOST, _BOOST_ERR
-    if _BOOST is not None:
-        return _BOOST
-    if _BOOST_ERR is not None:
-        raise RuntimeError(f"native gfx950 keyterm boosting library unavailable: {_BOOST_ERR}") from _BOOST_ERR
-    try:
-        from . import _vwa_boost as m  # type: ignore
-
-        _BOOST = m
-        return m
-    except BaseException as e:  # noqa: BLE001
-        _BOOST_ERR = e
-        raise RuntimeError(
-            "native gfx950 keyterm boosting library _vwa_boost.so failed to load; build it with "
-            "`python -m voice_enabled_browser_automation_amd.ops.build`"
-        ) from e
+    """The keyterm boosting library ``_vwa_boost.so`` (loaded once). Raises if unavailable."""
+    return _load_lib("_vwa_boost", "keyterm boosting")
 
 
 def boost_step(logits: torch.Tensor, vocab: int, tables, roots: torch.Tensor, state_in: torch.Tensor,
@@ -1680,30 +1635,13 @@ def boost_step(logits: torch.Tensor, vocab: int, tables, roots: torch.Tensor, st
 
 
 # ----------------------------------------------------------------------------- timestamp rules
-_TSRULES = None
-_TSRULES_ERR: Optional[BaseException] = None
 TS_MAX_ROWS = 64          # csrc/tsrules/tsrules.h kTsMaxRows: rows per launch
 TS_MAX_VOCAB = 1 << 20    # ... kTsMaxVocab
 
 
 def ts_rules_ext():
-    """Load the timestamp rules library ``_vwa_tsrules.so`` (once). Raises if unavailable."""
-    global _TSRULES, _TSRULES_ERR
-    if _TSRULES is not None:
-        return _TSRULES
-    if _TSRULES_ERR is not None:
-        raise RuntimeError(f"native gfx950 timestamp rules library unavailable: {_TSRULES_ERR}") from _TSRULES_ERR
-    try:
-        from . import _vwa_tsrules as m  # type: ignore
-
-        _TSRULES = m
-        return m
-    except BaseException as e:  # noqa: BLE001
-        _TSRULES_ERR = e
-        raise RuntimeError(
-            "native gfx950 timestamp rules library _vwa_tsrules.so failed to load; build it with "
-            "`python -m voice_enabled_browser_automation_amd.ops.build`"
-        ) from e
+    """The timestamp rules library ``_vwa_tsrules.so`` (loaded once). Raises if unavailable."""
+    return _load_lib("_vwa_tsrules", "timestamp rules")
 
 
 def ts_rules_step(logits: torch.Tensor, vocab: int, eot: int, ts_begin: int, max_initial: int, mask: torch.Tensor,
@@ -1767,30 +1705,13 @@ def ts_rules_step(logits: torch.Tensor, vocab: int, eot: int, ts_begin: int, max
 
 
 # ----------------------------------------------------------------------------- transcript scores
-_SCORE = None
-_SCORE_ERR: Optional[BaseException] = None
 SCORE_MAX_ROWS = 64          # csrc/score/score.h kScoreMaxRows: rows per launch
 SCORE_MAX_VOCAB = 1 << 20    # ... kScoreMaxVocab
 
 
 def score_ext():
-    """Load the transcript score library ``_vwa_score.so`` (once). Raises if unavailable."""
-    global _SCORE, _SCORE_ERR
-    if _SCORE is not None:
-        return _SCORE
-    if _SCORE_ERR is not None:
-        raise RuntimeError(f"native gfx950 transcript score library unavailable: {_SCORE_ERR}") from _SCORE_ERR
-    try:
-        from . import _vwa_score as m  # type: ignore
-
-        _SCORE = m
-        return m
-    except BaseException as e:  # noqa: BLE001
-        _SCORE_ERR = e
-        raise RuntimeError(
-            "native gfx950 transcript score library _vwa_score.so failed to load; build it with "
-            "`python -m voice_enabled_browser_automation_amd.ops.build`"
-        ) from e
+    """The transcript score library ``_vwa_score.so`` (loaded once). Raises if unavailable."""
+    return _load_lib("_vwa_score", "transcript score")
 
 
 def score_step(logits: torch.Tensor, vocab: int, eot: int, mask: torch.Tensor, enable: torch.Tensor,

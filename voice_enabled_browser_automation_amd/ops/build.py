@@ -1,19 +1,26 @@
 """Native build driver (no setuptools/hipify involved).
 
-* ``_vwa_kernels.so`` -- the gfx950 HIP kernel library + torch bindings. Every ``csrc/kernels/*.hip``
-  is compiled with ``hipcc --offload-arch=gfx950`` into its own object (parallel, incremental),
-  ``csrc/bindings.cpp`` is compiled against the torch headers, and the lot is linked against
-  torch's own HIP runtime (same ``libamdhip64.so.7`` soname, so one HIP runtime per process).
-* ``_vwa_align.so`` -- the word-alignment kernels (``csrc/align/*.hip`` + its own ``bindings.cpp``),
-  built and linked the same way into a library of its own.
-* ``_vwa_sot.so`` -- the start-of-transcript probe (``csrc/sot/*.hip`` + its own ``bindings.cpp``),
-  likewise.
-* ``_vwa_beam.so`` -- the beam search steps (``csrc/beam/*.hip`` + its own ``bindings.cpp``), likewise.
-* ``_vwa_boost.so`` -- the keyterm boosting step (``csrc/boost/*.hip`` + its own ``bindings.cpp``), likewise.
-* ``_vwa_tsrules.so`` -- the timestamp rules step (``csrc/tsrules/*.hip`` + its own ``bindings.cpp``), likewise.
-* ``_vwa_score.so`` -- the transcript score step (``csrc/score/*.hip`` + its own ``bindings.cpp``), likewise.
-* ``_vwa_native.so`` -- the CPU runtime library (grammar engine, KV block manager): plain C++17
-  with pybind11, built with g++.
+The gfx950 HIP kernel libraries, one row of ``KERNEL_LIBS`` each:
+
+================  ====================  ===============================================
+sources           library               what
+================  ====================  ===============================================
+``csrc/kernels``  ``_vwa_kernels.so``   the main kernel library (GEMMs, attention, ...)
+``csrc/align``    ``_vwa_align.so``     word alignment
+``csrc/sot``      ``_vwa_sot.so``       start-of-transcript probe
+``csrc/beam``     ``_vwa_beam.so``      beam search steps
+``csrc/boost``    ``_vwa_boost.so``     keyterm boosting step
+``csrc/tsrules``  ``_vwa_tsrules.so``   timestamp rules step
+``csrc/score``    ``_vwa_score.so``     transcript score step
+================  ====================  ===============================================
+
+Every ``*.hip`` of a library's directory is compiled with ``hipcc --offload-arch=gfx950`` into its
+own object (parallel, incremental), its ``bindings.cpp`` (the main library's: ``csrc/bindings.cpp``)
+is compiled against the torch headers, and the lot is linked against torch's own HIP runtime (same
+``libamdhip64.so.7`` soname, so one HIP runtime per process).
+
+``_vwa_native.so`` is the CPU runtime library (grammar engine, KV block manager): plain C++17 with
+pybind11, built with g++.
 
 All land in-tree next to this file so they travel with the repo snapshot to the GPU box.
 Run: ``python -m voice_enabled_browser_automation_amd.ops.build [--force]``.
@@ -34,14 +41,15 @@ BUILD = os.path.join(REPO, "build", "native")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-KERNEL_SO = os.path.join(HERE, "_vwa_kernels.so")
+# (source directory under csrc/, extension name); the first row is the main library
+KERNEL_LIBS = (("kernels", "_vwa_kernels"), ("align", "_vwa_align"), ("sot", "_vwa_sot"), ("beam", "_vwa_beam"),
+               ("boost", "_vwa_boost"), ("tsrules", "_vwa_tsrules"), ("score", "_vwa_score"))
+KERNEL_SO, ALIGN_SO, SOT_SO, BEAM_SO, BOOST_SO, TSRULES_SO, SCORE_SO = (
+    os.path.join(HERE, ext_name + ".so") for _, ext_name in KERNEL_LIBS)
 NATIVE_SO = os.path.join(HERE, "_vwa_native.so")
-ALIGN_SO = os.path.join(HERE, "_vwa_align.so")
-SOT_SO = os.path.join(HERE, "_vwa_sot.so")
-BEAM_SO = os.path.join(HERE, "_vwa_beam.so")
-BOOST_SO = os.path.join(HERE, "_vwa_boost.so")
-TSRULES_SO = os.path.join(HERE, "_vwa_tsrules.so")
-SCORE_SO = os.path.join(HERE, "_vwa_score.so")
+# headers any library's sources may include, besides those of its own directory
+SHARED_HEADERS = [os.path.join(CSRC, "torch_checks.h"), os.path.join(CSRC, "kernels", "common.h"),
+                  os.path.join(CSRC, "kernels", "logit_row.h")]
 
 
 def _torch_paths():
@@ -78,48 +86,17 @@ def _run(cmd: list[str]) -> None:
         raise RuntimeError("build step failed: " + " ".join(cmd[:6]) + " ...")
 
 
-def build_kernels(force: bool = False, jobs: int = 8) -> str:
-    os.makedirs(BUILD, exist_ok=True)
-    inc, lib, abi = _torch_paths()
-    headers = glob.glob(os.path.join(CSRC, "kernels", "*.h"))
-    kern_src = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")))
-    common = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result",
-              "-I", os.path.join(CSRC)] + os.environ.get("VWA_HIPCC_EXTRA", "").split()  # (utils/env.py Settings documents it; build.py stays import-light)  # (experiments)
-    jobs_list = []
-    objs = []
-    for src in kern_src:
-        obj = os.path.join(BUILD, os.path.basename(src) + ".o")
-        objs.append(obj)
-        if force or not _newer(obj, [src] + headers):
-            jobs_list.append(common + ["-c", src, "-o", obj])
-    bind_src = os.path.join(CSRC, "bindings.cpp")
-    bind_obj = os.path.join(BUILD, "bindings.o")
-    objs.append(bind_obj)
-    if force or not _newer(bind_obj, [bind_src] + headers):
-        cmd = common + ["-c", bind_src, "-o", bind_obj, f"-D_GLIBCXX_USE_CXX11_ABI={abi}",
-                        "-DTORCH_EXTENSION_NAME=_vwa_kernels", "-DUSE_ROCM=1", "-I", _py_include()]
-        for i in inc:
-            cmd += ["-I", i]
-        jobs_list.append(cmd)
-    with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
-        list(ex.map(_run, jobs_list))
-    if force or jobs_list or not _newer(KERNEL_SO, objs):
-        link = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", KERNEL_SO] + objs + [
-            "-L", lib, "-ltorch", "-ltorch_cpu", "-ltorch_python", "-lc10", "-lc10_hip", "-ltorch_hip",
-            f"-Wl,-rpath,{lib}"]
-        _run(link)
-    return KERNEL_SO
-
-
-def _build_kernel_lib(sub: str, so: str, ext_name: str, force: bool, jobs: int) -> str:
-    """A kernel library of its own: csrc/<sub>/*.hip + csrc/<sub>/bindings.cpp -> ``so`` (objects
-    under build/native/<sub>; the shared device helpers come from csrc/kernels/common.h)."""
-    bdir = os.path.join(BUILD, sub)
+def _build_kernel_lib(sub: str, ext_name: str, force: bool, jobs: int) -> str:
+    """One row of KERNEL_LIBS: csrc/<sub>/*.hip + csrc/<sub>/bindings.cpp -> <ext_name>.so, objects under
+    build/native/<sub>.  The main library's bindings are csrc/bindings.cpp and its objects build/native."""
+    main = sub == KERNEL_LIBS[0][0]
+    so = os.path.join(HERE, ext_name + ".so")
+    bdir = BUILD if main else os.path.join(BUILD, sub)
     os.makedirs(bdir, exist_ok=True)
     inc, lib, abi = _torch_paths()
-    headers = glob.glob(os.path.join(CSRC, sub, "*.h")) + [os.path.join(CSRC, "kernels", "common.h")]
+    headers = glob.glob(os.path.join(CSRC, sub, "*.h")) + SHARED_HEADERS
     common = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result",
-              "-I", os.path.join(CSRC)] + os.environ.get("VWA_HIPCC_EXTRA", "").split()
+              "-I", os.path.join(CSRC)] + os.environ.get("VWA_HIPCC_EXTRA", "").split()  # (utils/env.py Settings documents it; build.py stays import-light)
     jobs_list = []
     objs = []
     for src in sorted(glob.glob(os.path.join(CSRC, sub, "*.hip"))):
@@ -127,7 +104,7 @@ def _build_kernel_lib(sub: str, so: str, ext_name: str, force: bool, jobs: int) 
         objs.append(obj)
         if force or not _newer(obj, [src] + headers):
             jobs_list.append(common + ["-c", src, "-o", obj])
-    bind_src = os.path.join(CSRC, sub, "bindings.cpp")
+    bind_src = os.path.join(CSRC, "bindings.cpp") if main else os.path.join(CSRC, sub, "bindings.cpp")
     bind_obj = os.path.join(bdir, "bindings.o")
     objs.append(bind_obj)
     if force or not _newer(bind_obj, [bind_src] + headers):
@@ -145,34 +122,9 @@ def _build_kernel_lib(sub: str, so: str, ext_name: str, force: bool, jobs: int) 
     return so
 
 
-def build_align(force: bool = False, jobs: int = 8) -> str:
-    """Word-alignment kernel library: csrc/align -> _vwa_align.so."""
-    return _build_kernel_lib("align", ALIGN_SO, "_vwa_align", force, jobs)
-
-
-def build_sot(force: bool = False, jobs: int = 8) -> str:
-    """Start-of-transcript probe library (language detection, no-speech gate): csrc/sot -> _vwa_sot.so."""
-    return _build_kernel_lib("sot", SOT_SO, "_vwa_sot", force, jobs)
-
-
-def build_beam(force: bool = False, jobs: int = 8) -> str:
-    """Beam search library (candidate selection, K/V following the parents): csrc/beam -> _vwa_beam.so."""
-    return _build_kernel_lib("beam", BEAM_SO, "_vwa_beam", force, jobs)
-
-
-def build_boost(force: bool = False, jobs: int = 8) -> str:
-    """Keyterm boosting library (automaton step + logit bias, one launch): csrc/boost -> _vwa_boost.so."""
-    return _build_kernel_lib("boost", BOOST_SO, "_vwa_boost", force, jobs)
-
-
-def build_tsrules(force: bool = False, jobs: int = 8) -> str:
-    """Timestamp rules library (state step + logit bans, one launch): csrc/tsrules -> _vwa_tsrules.so."""
-    return _build_kernel_lib("tsrules", TSRULES_SO, "_vwa_tsrules", force, jobs)
-
-
-def build_score(force: bool = False, jobs: int = 8) -> str:
-    """Transcript score library (the sampled tokens' log-probabilities, one launch): csrc/score -> _vwa_score.so."""
-    return _build_kernel_lib("score", SCORE_SO, "_vwa_score", force, jobs)
+def build_kernels(force: bool = False, jobs: int = 8) -> str:
+    """The main kernel library: csrc/kernels + csrc/bindings.cpp -> _vwa_kernels.so."""
+    return _build_kernel_lib(*KERNEL_LIBS[0], force, jobs)
 
 
 def build_native(force: bool = False) -> str:
@@ -195,13 +147,8 @@ def build_all(force: bool = False) -> list[str]:
     n = build_native(force)
     if n:
         out.append(n)
-    out.append(build_kernels(force))
-    out.append(build_align(force))
-    out.append(build_sot(force))
-    out.append(build_beam(force))
-    out.append(build_boost(force))
-    out.append(build_tsrules(force))
-    out.append(build_score(force))
+    for sub, ext_name in KERNEL_LIBS:
+        out.append(_build_kernel_lib(sub, ext_name, force, 8))
     return out
 
 
