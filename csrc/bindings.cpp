@@ -184,7 +184,7 @@ int run_skinny(int epi, const SkinnyParams& p, hipStream_t st) {
 // x (the anchor), w and bias of a skinny GEMM; xn / wn / bn: the entry point's names for them
 SkinnyParams base_params(const Tensor& x, const char* xn, const Tensor& w, const char* wn, const OptTensor& bias,
                          const char* bn, bool fuse_rms, double eps, const OptTensor& w_scale = c10::nullopt,
-                         bool w_tiled = false) {
+                         bool w_tiled = false, bool w_nt = false) {
   check_gpu(x, x, kBF16, xn);
   check_rows(x, xn);
   check_gpu(w, x, w_scale.has_value() ? kF8 : kBF16, wn);
@@ -199,6 +199,8 @@ SkinnyParams base_params(const Tensor& x, const char* xn, const Tensor& w, const
   if (bias.has_value()) check_vec(*bias, x, kBF16, w.size(0), bn, true);
   // (fp8 + tiled: the fp8 tiled layout, which only the streaming kernel's W8A8 path reads)
   if (w_tiled) TORCH_CHECK(w.size(0) % 16 == 0, "pre-tiled weights need N % 16 == 0, K % 128 == 0");
+  // (the nt weight policy reads whole lines once per instruction: the pre-tiled layouts only)
+  TORCH_CHECK(!w_nt || w_tiled, wn, ": w_nt (non-temporal weight loads) needs a pre-tiled weight");
   SkinnyParams p{};
   p.X = bfp(x);
   p.ldx = (int)x.stride(0);
@@ -212,6 +214,7 @@ SkinnyParams base_params(const Tensor& x, const char* xn, const Tensor& w, const
   p.w_scale = ptr_opt<float>(w_scale);
   p.w_first = g_w_first == 2 || (g_w_first == 1 && fuse_rms);
   p.w_tiled = w_tiled ? 1 : 0;
+  p.w_nt = w_nt ? 1 : 0;
   return p;
 }
 
@@ -243,9 +246,9 @@ void set_ln_fold(SkinnyParams& p, const Tensor& a, const OptTensor& ln_c, int ep
 // the first mask_rows rows are not computed (their y columns are left as they were)
 void skinny_gemm(Tensor x, Tensor w, OptTensor bias, Tensor y, int64_t epi, bool fuse_rms, double eps,
                  OptTensor residual, OptTensor w_scale, OptTensor ln_c, bool w_tiled, OptTensor col_mask,
-                 int64_t col_mask_off, int64_t mask_rows) {
+                 int64_t col_mask_off, int64_t mask_rows, bool w_nt) {
   c10::DeviceGuard g(x.device());
-  SkinnyParams p = base_params(x, "x", w, "w", bias, "bias", fuse_rms, eps, w_scale, w_tiled);
+  SkinnyParams p = base_params(x, "x", w, "w", bias, "bias", fuse_rms, eps, w_scale, w_tiled, w_nt);
   TORCH_CHECK(epi == 0 || epi == 1 || epi == 3, "bad epilogue");
   set_ln_fold(p, x, ln_c, (int)epi);
   check_gpu(y, x, bf16_or_f32(y), "y");
@@ -278,9 +281,9 @@ void skinny_gemm(Tensor x, Tensor w, OptTensor bias, Tensor y, int64_t epi, bool
 }
 
 void skinny_gemm_swiglu(Tensor x, Tensor w_gu, OptTensor bias, Tensor h, bool fuse_rms, double eps, OptTensor w_scale,
-                        bool w_tiled) {
+                        bool w_tiled, bool w_nt) {
   c10::DeviceGuard g(x.device());
-  SkinnyParams p = base_params(x, "x", w_gu, "w_gu", bias, "bias", fuse_rms, eps, w_scale, w_tiled);
+  SkinnyParams p = base_params(x, "x", w_gu, "w_gu", bias, "bias", fuse_rms, eps, w_scale, w_tiled, w_nt);
   check_gpu(h, x, kBF16, "h");
   check_rows_weak(h, "h");
   TORCH_CHECK(w_gu.size(0) % 32 == 0, "gate/up rows must be a multiple of 32");
@@ -293,9 +296,9 @@ void skinny_gemm_swiglu(Tensor x, Tensor w_gu, OptTensor bias, Tensor h, bool fu
 void skinny_gemm_qkv(Tensor x, Tensor w_qkv, OptTensor bias, bool fuse_rms, double eps, int64_t n_q_heads,
                      int64_t n_kv_heads, int64_t head_dim, bool use_rope, Tensor positions, Tensor slots,
                      OptTensor rope, Tensor q_out, Tensor k_cache, Tensor v_cache, OptTensor w_scale, OptTensor ln_c,
-                     bool w_tiled) {
+                     bool w_tiled, bool w_nt) {
   c10::DeviceGuard g(x.device());
-  SkinnyParams p = base_params(x, "x", w_qkv, "w_qkv", bias, "bias", fuse_rms, eps, w_scale, w_tiled);
+  SkinnyParams p = base_params(x, "x", w_qkv, "w_qkv", bias, "bias", fuse_rms, eps, w_scale, w_tiled, w_nt);
   set_ln_fold(p, x, ln_c, 4);
   set_qkv(p, check_qkv(x, p.M, p.N, "w_qkv", n_q_heads, n_kv_heads, head_dim, use_rope, positions, slots, rope, q_out,
                        k_cache, v_cache));
@@ -768,9 +771,12 @@ std::tuple<Tensor, int64_t> chain_make(Tensor h, Tensor att, Tensor act, Tensor 
                                        OptTensor a_row_table, OptTensor s_o, OptTensor s_gu, OptTensor s_down,
                                        OptTensor s_qkv, int64_t tp_ar, OptTensor a_plan, int64_t a_plan_mode,
                                        OptTensor p_o, OptTensor p_gu, OptTensor p_down, OptTensor p_qkv,
-                                       std::vector<int64_t> p_base) {
+                                       std::vector<int64_t> p_base, bool w_nt) {
   c10::DeviceGuard g(h.device());
   ChainParams cp{};
+  // w_nt: the launch streams its weights non-temporally where it has that instantiation (the tails
+  // with the attention phase: packed, bf16 with o_nt2, fp8); other forms keep the default policy
+  TORCH_CHECK(!w_nt || w_tiled, "chain: w_nt (non-temporal weight loads) needs pre-tiled weights");
   // s_*: per-row scales of fp8 tiled weights (ops.tile_weight_fp8) -> the W8A16 chain
   TORCH_CHECK(s_o.has_value() == s_gu.has_value() && s_o.has_value() == s_down.has_value() &&
                   (!w_qkv.has_value() || s_qkv.has_value() == s_o.has_value()),
@@ -873,15 +879,17 @@ std::tuple<Tensor, int64_t> chain_make(Tensor h, Tensor att, Tensor act, Tensor 
       q.w_pack_base = (int)p_base[i];
     }
   }
+  for (int i = 0; i < cp.n; ++i) cp.ph[i].p.w_nt = w_nt ? 1 : 0;
   int64_t lds = 0;
   Tensor desc = chain_upload(cp, h, lds);
   if (!desc.numel()) return {desc, 0};
+  const bool nt = w_nt && cp.attn_g > 0 && !cp.ph[2].xg && (pk || s_o.has_value() != (cp.o_nt2 != 0));
   // (bit 24 of the returned LDS size: the down phase streams X with the weights, bit 25: fp8
-  // weights, bit 26: o_proj in 32-column tiles, bit 28: packed weights -- chain_run launches that
-  // instantiation)
+  // weights, bit 26: o_proj in 32-column tiles, bit 28: packed weights, bit 29: nt weight loads --
+  // chain_run launches that instantiation)
   return {desc, lds | (cp.n >= 3 && cp.ph[2].xg ? (int64_t)1 << 24 : 0) | (cp.d_nt2 ? (int64_t)1 << 27 : 0) |
                     (s_o.has_value() ? (int64_t)1 << 25 : 0) | (cp.o_nt2 ? (int64_t)1 << 26 : 0) |
-                    (pk ? (int64_t)1 << 28 : 0)};
+                    (pk ? (int64_t)1 << 28 : 0) | (nt ? (int64_t)1 << 29 : 0)};
 }
 
 // Whisper decoder chains (skinny_stream.hip chain_kernel SEQ 1 / 2): phase i computes
@@ -948,7 +956,7 @@ void chain_run(Tensor desc, int64_t n_phases, int64_t lds, Tensor like, int64_t 
   check_rc(vwa_chain_launch(reinterpret_cast<const ChainParams*>(desc.data_ptr()), (int)seq, (int)n_phases, (int)attn_g,
                             (int)(lds & 0xFFFFFF), chain_grid(like), cur_stream(like),
                             (int)((lds >> 24) & 1) * (((lds >> 27) & 1) ? 2 : 1), (int)((lds >> 25) & 1),
-                            (int)((lds >> 26) & 1), (int)n_layers, (int)((lds >> 28) & 1)),
+                            (int)((lds >> 26) & 1), (int)n_layers, (int)((lds >> 28) & 1), (int)((lds >> 29) & 1) * 2),
            "chain");
 }
 
@@ -1426,14 +1434,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm", &skinny_gemm, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("epi"),
         py::arg("fuse_rms"), py::arg("eps"), py::arg("residual"), py::arg("w_scale") = py::none(),
         py::arg("ln_c") = py::none(), py::arg("w_tiled") = false, py::arg("col_mask") = py::none(),
-        py::arg("col_mask_off") = 0, py::arg("mask_rows") = 1);
+        py::arg("col_mask_off") = 0, py::arg("mask_rows") = 1, py::arg("w_nt") = false);
   m.def("skinny_gemm_swiglu", &skinny_gemm_swiglu, py::arg("x"), py::arg("w_gu"), py::arg("bias"), py::arg("h"),
-        py::arg("fuse_rms"), py::arg("eps"), py::arg("w_scale") = py::none(), py::arg("w_tiled") = false);
+        py::arg("fuse_rms"), py::arg("eps"), py::arg("w_scale") = py::none(), py::arg("w_tiled") = false,
+        py::arg("w_nt") = false);
   m.def("skinny_gemm_qkv", &skinny_gemm_qkv, py::arg("x"), py::arg("w_qkv"), py::arg("bias"), py::arg("fuse_rms"),
         py::arg("eps"), py::arg("n_q_heads"), py::arg("n_kv_heads"), py::arg("head_dim"), py::arg("use_rope"),
         py::arg("positions"), py::arg("slots"), py::arg("rope"), py::arg("q_out"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("w_scale") = py::none(), py::arg("ln_c") = py::none(),
-        py::arg("w_tiled") = false);
+        py::arg("w_tiled") = false, py::arg("w_nt") = false);
   m.def("chain_make", &chain_make, py::arg("h"), py::arg("att"), py::arg("act"), py::arg("w_o"), py::arg("w_gu"),
         py::arg("w_down"), py::arg("eps"), py::arg("w_qkv"), py::arg("n_q_heads"), py::arg("n_kv_heads"),
         py::arg("head_dim"), py::arg("positions"), py::arg("slots"), py::arg("rope"), py::arg("q_out"),
@@ -1446,7 +1455,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("s_o") = py::none(), py::arg("s_gu") = py::none(), py::arg("s_down") = py::none(),
         py::arg("s_qkv") = py::none(), py::arg("tp_ar") = 0, py::arg("a_plan") = py::none(), py::arg("a_plan_mode") = 0,
         py::arg("p_o") = py::none(), py::arg("p_gu") = py::none(), py::arg("p_down") = py::none(),
-        py::arg("p_qkv") = py::none(), py::arg("p_base") = std::vector<int64_t>{});
+        py::arg("p_qkv") = py::none(), py::arg("p_base") = std::vector<int64_t>{}, py::arg("w_nt") = false);
   m.def("set_small_gemm_bytes", &set_small_gemm_bytes);
   m.def("gemm_set_p8", [](int64_t mode) { vwa_gemm_set_p8((int)mode); });
   m.def("skinny_set_x_skew", [](int64_t skew) { vwa_skinny_set_x_skew((int)skew); });

@@ -213,7 +213,9 @@ VWA_DEVICE void tile_epilogue(const SkinnyParams& p, float* red, const float* rs
 
 // MT: 16-row MFMA row fragments per weight fragment (only MT = 1 is instantiated since round 5: the
 // 17..64-row form measured slower than the tiled GEMM and was removed).
-template <int EPI, int NT, int KS, bool XG, int MT = 1>
+// AUX: cache policy of the pre-tiled weight loads (bload_w; SkinnyParams::w_nt -> 2).  The row-major
+// branch, whose 16-byte pieces share each cache line among several instructions, keeps policy 0.
+template <int EPI, int NT, int KS, bool XG, int MT = 1, int AUX = 0>
 __global__ __launch_bounds__(KS * 64) void skinny_stream_kernel(SkinnyParams p, int nb, int xstride, int xskew) {
   // k-groups (128 wide) per item; MT > 1: one (the X fragments of MT row tiles share the
   // register budget of the item's weights)
@@ -293,7 +295,7 @@ __global__ __launch_bounds__(KS * 64) void skinny_stream_kernel(SkinnyParams p, 
           const unsigned T = (unsigned)(tile * NT + nt);
           const unsigned base = ((T * (unsigned)G + (unsigned)kg) * 4u) * 1024u + (unsigned)lane * 16u;
 #pragma unroll
-          for (int s = 0; s < 4; ++s) wr[nt][u][s] = bload(rw, ok ? base + 1024u * s : kOOB);
+          for (int s = 0; s < 4; ++s) wr[nt][u][s] = bload_w<AUX>(rw, ok ? base + 1024u * s : kOOB);
         } else {
           const unsigned row = (unsigned)(tile * 16 * NT + nt * 16 + nl);
           const unsigned base = (row * (unsigned)K + (unsigned)(kg * 128 + 32 * g)) * 2u;
@@ -404,7 +406,7 @@ __global__ __launch_bounds__(KS * 64) void skinny_stream_kernel(SkinnyParams p, 
 
 int g_x_skew = 32;  // LDS X row skew (elements per 4 rows; 0: none -- A/B knob, vwa_skinny_set_x_skew)
 
-template <int EPI, int NT, int KS, bool XG, int MT = 1>
+template <int EPI, int NT, int KS, bool XG, int MT = 1, int AUX = 0>
 int launch_v(const SkinnyParams& p, hipStream_t st, int grid_cap, size_t lds, int xstride) {
   constexpr int U = MT > 1 ? 1 : XG ? 2 : 4 / NT;
   const int G = p.K / 128;
@@ -412,12 +414,12 @@ int launch_v(const SkinnyParams& p, hipStream_t st, int grid_cap, size_t lds, in
   const int nb = (per_wave + U - 1) / U;
   const int ntiles = p.N / (16 * NT);
   const int grid = ntiles < grid_cap ? ntiles : grid_cap;
-  hipLaunchKernelGGL((skinny_stream_kernel<EPI, NT, KS, XG, MT>), dim3(grid), dim3(KS * 64), lds, st, p, nb, xstride,
+  hipLaunchKernelGGL((skinny_stream_kernel<EPI, NT, KS, XG, MT, AUX>), dim3(grid), dim3(KS * 64), lds, st, p, nb, xstride,
                      XG ? 0 : g_x_skew);
   return 0;
 }
 
-template <int EPI, int NT, int KS>
+template <int EPI, int NT, int KS, int AUX = 0>
 int launch(const SkinnyParams& p0, hipStream_t st, int grid_cap) {
   SkinnyParams p = p0;
   const int xstride = p.K + 8;
@@ -435,9 +437,10 @@ int launch(const SkinnyParams& p0, hipStream_t st, int grid_cap) {
     if (EPI != EPI_STORE || NT != 1 || !lds_x || (ntiles + grid - 1) / grid > 64 || p.col_mask_rows < 1)
       p.col_mask = nullptr;
   }
-  if (lds_x) return launch_v<EPI, NT, KS, false>(p, st, grid_cap, xbytes + red, xstride);
+  if (lds_x) return launch_v<EPI, NT, KS, false, 1, AUX>(p, st, grid_cap, xbytes + red, xstride);
   if ((size_t)p.M * p.ldx * 2 >= 0x7FFFFFF0ull) return -10;
-  return launch_v<EPI, NT, KS, true>(p, st, grid_cap, red, xstride);
+  // (X streaming with the nt weight policy: the residual epilogue only -- the Llama down projection)
+  return launch_v<EPI, NT, KS, true, 1, EPI == EPI_RESID ? AUX : 0>(p, st, grid_cap, red, xstride);
 }
 
 
@@ -447,7 +450,11 @@ int launch(const SkinnyParams& p0, hipStream_t st, int grid_cap) {
 // amax/448), the inner product runs on the fp8 MFMA (16x16x32, 8 bytes per lane per operand),
 // and both scales are applied in the epilogue.  Weight bytes per decode step are halved.
 // ------------------------------------------------------------------------------------------
-template <int EPI, int NT, int KS>
+// AUX: as skinny_stream_kernel's.  TILED: the weight is known to be in the fp8 tiled layout, the
+// row-major branch is compiled out -- the form tiled weights run at 8 waves, so that the nt kernel and
+// its default-policy twin differ in the policy bits of their loads and in nothing else (with the
+// run-time branch the compiler merges the two layouts' loads only when both have one policy)
+template <int EPI, int NT, int KS, int AUX = 0, bool TILED = false>
 __global__ __launch_bounds__(KS * 64) void skinny_fp8_kernel(SkinnyParams p, int nb, int xstride) {
   constexpr int U = 8 / NT;  // k-groups (128 wide) per item: 2 x b128 weight loads per k-group
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -519,14 +526,14 @@ __global__ __launch_bounds__(KS * 64) void skinny_fp8_kernel(SkinnyParams p, int
       const bool ok = (it < n_items) && (kg < ge);
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
-        if (p.w_tiled) {
+        if (TILED || p.w_tiled) {
           // fp8 tiled layout (ops.tile_weight_fp8): the (16-row tile, k-group) block is 2 KB
           // [s][lane][16 B] -- each load instruction reads 1 KB contiguous, lane (nl, g) gets
           // W[row][128 kg + 32 g + 16 s .. + 16), the same bytes as the row-major addressing below
           const unsigned T = (unsigned)(tile * NT + nt);
           const unsigned base = (T * (unsigned)G + (unsigned)kg) * 2048u + (unsigned)lane * 16u;
 #pragma unroll
-          for (int s = 0; s < 2; ++s) wr[nt][u][s] = bload(rw, ok ? base + 1024u * s : kOOB);
+          for (int s = 0; s < 2; ++s) wr[nt][u][s] = bload_w<AUX>(rw, ok ? base + 1024u * s : kOOB);
         } else {
           const unsigned row = (unsigned)(tile * 16 * NT + nt * 16 + nl);
           const unsigned base = row * (unsigned)K + (unsigned)(kg * 128 + 32 * g);
@@ -579,7 +586,7 @@ __global__ __launch_bounds__(KS * 64) void skinny_fp8_kernel(SkinnyParams p, int
   }
 }
 
-template <int EPI, int NT, int KS>
+template <int EPI, int NT, int KS, int AUX = 0, bool TILED = false>
 int launch_fp8(const SkinnyParams& p, hipStream_t st, int grid_cap) {
   constexpr int U = 8 / NT;
   // skinny_fp8_kernel holds 16 rows (rs[16], one MFMA row fragment): more rows must go to the
@@ -594,7 +601,7 @@ int launch_fp8(const SkinnyParams& p, hipStream_t st, int grid_cap) {
   if (lds > 160 * 1024) return -10;
   const int ntiles = p.N / (16 * NT);
   const int grid = ntiles < grid_cap ? ntiles : grid_cap;
-  hipLaunchKernelGGL((skinny_fp8_kernel<EPI, NT, KS>), dim3(grid), dim3(KS * 64), lds, st, p, nb, xstride);
+  hipLaunchKernelGGL((skinny_fp8_kernel<EPI, NT, KS, AUX, TILED>), dim3(grid), dim3(KS * 64), lds, st, p, nb, xstride);
   return 0;
 }
 
@@ -959,7 +966,7 @@ VWA_DEVICE void chain_load(const SkinnyParams& p, int nb, uint4 (&wr)[R], int it
         const unsigned base = (row * (unsigned)p.K + (unsigned)(kg * 128 + 32 * g)) * 2u;
         const unsigned vb = ok ? base : kOOB2;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) wr[(nt * U + u) * 4 + s] = bload_w_so<WA>(rw, vb, 16 * s);
+        for (int s = 0; s < 4; ++s) wr[(nt * U + u) * 4 + s] = bload_w_so<0>(rw, vb, 16 * s);  // (row-major: never WA)
       }
     }
     if constexpr (XG) {
@@ -1527,9 +1534,12 @@ VWA_DEVICE void kv_prefetch(const DecodeAttnParams& a, int ev, unsigned char* ld
 // ramp, and the HBM pipe of half the CUs is busy through the QKV tail and the attention front.
 // (Skipping the wait is safe for the ticket barriers: such a workgroup's next arrival happens only
 // after the attention hand-off, which itself needed this barrier complete.)
+// WA: cache policy of the weight stream (buffer aux bits, bload_w): the tiled 1 KB loads, the packed
+// low-byte / nibble / sign loads and the LDS-DMA items.  Nothing else takes it: row-major weights,
+// pack_flag bytes, the flagged-block refetch, X / partial tiles (sc1), K/V, tables, barrier words.
 template <int KS, int SEQ, int NPH, int AG, int WA, bool XG2 = false, bool F8 = false, bool O2 = false, bool D2 = false,
           bool MULTI = false, bool PK = false>
-__global__ __launch_bounds__(KS * 64) void chain_kernel(const ChainParams* __restrict__ cpp, int n_layers) {
+VWA_DEVICE void chain_body(const ChainParams* __restrict__ cpp, int n_layers) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   static_assert(!MULTI || (SEQ == 0 && NPH == 4 && AG > 0 && !XG2), "multi-layer launch: Llama tails with attention");
   // PK: every phase streams the packed form of its bf16 weights (SkinnyParams::w_pack)
@@ -1814,6 +1824,20 @@ __global__ __launch_bounds__(KS * 64) void chain_kernel(const ChainParams* __res
   }  // layers
 }
 
+template <int KS, int SEQ, int NPH, int AG, int WA, bool XG2 = false, bool F8 = false, bool O2 = false, bool D2 = false,
+          bool MULTI = false, bool PK = false>
+__global__ __launch_bounds__(KS * 64) void chain_kernel(const ChainParams* __restrict__ cpp, int n_layers) {
+  chain_body<KS, SEQ, NPH, AG, WA, XG2, F8, O2, D2, MULTI, PK>(cpp, n_layers);
+}
+
+// The Llama tails with the attention phase over a weight stream loaded non-temporally (chain_body
+// WA = 2; the phases' SkinnyParams::w_nt, VWA_CHAIN_WNT): the same items, MFMAs, barriers and register sets as
+// chain_kernel's -- a kernel name of its own, so that a trace tells the two policies apart.
+template <int NPH, int AG, bool F8, bool O2, bool MULTI, bool PK>
+__global__ __launch_bounds__(8 * 64) void chain_wnt_kernel(const ChainParams* __restrict__ cpp, int n_layers) {
+  chain_body<8, 0, NPH, AG, 2, false, F8, O2, false, MULTI, PK>(cpp, n_layers);
+}
+
 }  // namespace
 
 // Host side: fill nt / nb of every phase and return the dynamic LDS bytes the chain needs, or
@@ -1856,6 +1880,9 @@ extern "C" int vwa_chain_prepare(ChainParams* cp, int grid) {
     // o_proj in 32-column tiles (checked below, once o_nt2 is settled), <= 4 rows, one rank
     const bool pk = p.w_pack != nullptr;
     if (i > 0 && pk != (cp->ph[0].p.w_pack != nullptr)) return -10;
+    // nt weight policy (w_nt, vwa_chain_launch wa = 2): every phase or none, pre-tiled weights only
+    // -- a row-major weight's cache lines are shared by several load instructions
+    if ((p.w_nt != 0) != (cp->ph[0].p.w_nt != 0) || (p.w_nt && !p.w_tiled)) return -10;
     if (pk && (f8 || !p.w_tiled || !p.w_pack_flag || p.w_pack_base < 0 || p.w_pack_base > 112 || cp->seq != 0 ||
                cp->attn_g == 0 || cp->tp.world > 1 || !(i == 0 ? ph.nt == 2 : cp->o_nt2)))
       return -10;
@@ -1937,8 +1964,31 @@ extern "C" int vwa_chain_prepare(ChainParams* cp, int grid) {
 }
 
 extern "C" int vwa_chain_launch(const ChainParams* d_cp, int seq, int n_phases, int attn_g, int lds, int grid,
-                                hipStream_t st, int xg2, int f8, int o2, int n_layers, int pk) {
+                                hipStream_t st, int xg2, int f8, int o2, int n_layers, int pk, int wa) {
   if (attn_g) lds = lds > (int)MqLds<128, 8>::bytes ? lds : (int)MqLds<128, 8>::bytes;
+  if (wa != 0 && wa != 2) return -10;
+  if (wa) {  // nt weight stream (chain_wnt_kernel): the Llama tails with the attention phase -- packed, bf16 o_nt2, fp8
+    if (seq != 0 || xg2 || (attn_g != 4 && attn_g != 8) || (n_phases != 3 && n_phases != 4)) return -10;
+    if (pk ? (f8 || !o2) : ((f8 != 0) == (o2 != 0))) return -10;
+    if (n_layers > 1 && n_phases != 4) return -10;
+#define VWA_CHAIN_LAUNCH_WNT(N, G, F8_, O2_, MULTI_, PK_) \
+  hipLaunchKernelGGL((chain_wnt_kernel<N, G, F8_, O2_, MULTI_, PK_>), dim3(grid), dim3(8 * 64), lds, st, d_cp, n_layers)
+#define VWA_CHAIN_LAUNCH_WNT_G(N, F8_, O2_, MULTI_, PK_) \
+  do { if (attn_g == 4) VWA_CHAIN_LAUNCH_WNT(N, 4, F8_, O2_, MULTI_, PK_); else VWA_CHAIN_LAUNCH_WNT(N, 8, F8_, O2_, MULTI_, PK_); } while (0)
+#define VWA_CHAIN_LAUNCH_WNT_FORM(F8_, O2_, PK_) \
+  do { \
+    if (n_layers > 1) VWA_CHAIN_LAUNCH_WNT_G(4, F8_, O2_, true, PK_); \
+    else if (n_phases == 4) VWA_CHAIN_LAUNCH_WNT_G(4, F8_, O2_, false, PK_); \
+    else VWA_CHAIN_LAUNCH_WNT_G(3, F8_, O2_, false, PK_); \
+  } while (0)
+    if (pk) VWA_CHAIN_LAUNCH_WNT_FORM(false, true, true);
+    else if (f8) VWA_CHAIN_LAUNCH_WNT_FORM(true, false, false);
+    else VWA_CHAIN_LAUNCH_WNT_FORM(false, true, false);
+#undef VWA_CHAIN_LAUNCH_WNT_FORM
+#undef VWA_CHAIN_LAUNCH_WNT_G
+#undef VWA_CHAIN_LAUNCH_WNT
+    return (int)hipGetLastError();
+  }
   if (pk) {  // packed bf16 weights (SkinnyParams::w_pack): Llama tail with attention, o_proj in 32-column tiles
     if (seq != 0 || f8 || xg2 || !o2 || (attn_g != 4 && attn_g != 8) || (n_phases != 3 && n_phases != 4)) return -10;
     if (n_layers > 1 && n_phases != 4) return -10;
@@ -2038,9 +2088,21 @@ extern "C" int vwa_chain_launch(const ChainParams* d_cp, int seq, int n_phases, 
 // 8 / 16 rows, profiles/r4_skinny_nt2_rows.jsonl, and were removed in round 5)
 
 // Returns -10 when this shape does not fit the streaming kernel (caller falls back).
-template <int KS>
+// AUX: the weight loads' cache policy (SkinnyParams::w_nt on pre-tiled weights -> 2).  Only what a
+// Llama decode step launches has an nt instantiation: the store, residual, SwiGLU and QKV epilogues
+// at 8 waves; GELU (Whisper, GPT-2) stays on the default policy.
+template <int KS, int AUX = 0>
 int dispatch_ks(int epi, const SkinnyParams& p, int grid_cap, hipStream_t st) {
   if (p.w_scale) {
+    if constexpr (KS == 8) {  // tiled weights: the kernels without the row-major branch (skinny_fp8_kernel TILED)
+      if (p.w_tiled) switch (epi) {
+          case EPI_STORE: return launch_fp8<EPI_STORE, 1, KS, AUX, true>(p, st, grid_cap);
+          case EPI_RESID: return launch_fp8<EPI_RESID, 1, KS, AUX, true>(p, st, grid_cap);
+          case EPI_SWIGLU: return launch_fp8<EPI_SWIGLU, 2, KS, AUX, true>(p, st, grid_cap);
+          case EPI_QKV: return launch_fp8<EPI_QKV, 1, KS, AUX, true>(p, st, grid_cap);
+          default: break;
+        }
+    }
     switch (epi) {
       case EPI_STORE: return launch_fp8<EPI_STORE, 1, KS>(p, st, grid_cap);
       case EPI_RESID: return launch_fp8<EPI_RESID, 1, KS>(p, st, grid_cap);
@@ -2051,11 +2113,11 @@ int dispatch_ks(int epi, const SkinnyParams& p, int grid_cap, hipStream_t st) {
     }
   }
   switch (epi) {
-    case EPI_STORE: return launch<EPI_STORE, 1, KS>(p, st, grid_cap);
-    case EPI_RESID: return launch<EPI_RESID, 1, KS>(p, st, grid_cap);
+    case EPI_STORE: return launch<EPI_STORE, 1, KS, AUX>(p, st, grid_cap);
+    case EPI_RESID: return launch<EPI_RESID, 1, KS, AUX>(p, st, grid_cap);
     case EPI_GELU: return launch<EPI_GELU, 1, KS>(p, st, grid_cap);
-    case EPI_SWIGLU: return launch<EPI_SWIGLU, 2, KS>(p, st, grid_cap);
-    case EPI_QKV: return launch<EPI_QKV, 1, KS>(p, st, grid_cap);
+    case EPI_SWIGLU: return launch<EPI_SWIGLU, 2, KS, AUX>(p, st, grid_cap);
+    case EPI_QKV: return launch<EPI_QKV, 1, KS, AUX>(p, st, grid_cap);
     default: return -3;
   }
 }
@@ -2070,7 +2132,10 @@ extern "C" int vwa_skinny_stream(int epi, const SkinnyParams* p, int grid_cap, i
 #ifdef VWA_ONLY_MULTI
   const int r = -10;
 #else
-  const int r = (ks == 4) ? dispatch_ks<4>(epi, *p, grid_cap, st) : dispatch_ks<8>(epi, *p, grid_cap, st);
+  // (w_nt on a row-major weight, or with the 4-wave split of K < 2048: the default policy)
+  const int r = (ks == 4)                  ? dispatch_ks<4>(epi, *p, grid_cap, st)
+                : (p->w_nt && p->w_tiled) ? dispatch_ks<8, 2>(epi, *p, grid_cap, st)
+                                          : dispatch_ks<8>(epi, *p, grid_cap, st);
 #endif
   if (r) return r;
   return (int)hipGetLastError();

@@ -48,6 +48,12 @@ struct SkinnyParams {
   // outside [w_pack_base, w_pack_base + 15] has w_pack_flag[T * (K / 128) + kg] != 0 and is read
   // from W instead, so every bf16 bit pattern is reproduced.  Null: W is streamed as it is.
   const uint8_t* w_pack; const uint8_t* w_pack_flag; int w_pack_base;
+  // w_nt (pre-tiled weights only, bf16 or fp8): W is read once per step by one CU and nothing of
+  // it survives in the caches until the next step (a Llama layer or LM-head weight), so the
+  // streaming kernel loads it non-temporally (buffer aux 2) where it has that instantiation.  Not
+  // for weights that are replayed out of the cache (Whisper's decoder) or re-read by several
+  // workgroups.  Row-major weights ignore it in the streaming kernel; a chain refuses them.
+  int w_nt;
 };
 
 // Paged / strided KV addressing shared by the attention kernels:
@@ -268,8 +274,11 @@ void vwa_skinny_set_x_skew(int skew);  // LDS-staged X rows: 64-B skew every 4 r
 int vwa_chain_prepare(ChainParams* cp, int grid);
 // n_layers > 1: d_cp is an array of n_layers descriptors of consecutive 4-phase Llama tails with the
 // attention phase, run by ONE launch (skinny_stream.hip chain_kernel MULTI)
+// wa: cache policy of the weight stream, 0 (default) or 2 (nt) -- 2 only for the Llama tails with the
+// attention phase (packed, bf16 with o_nt2, fp8) over descriptors whose phases carry w_nt
+// (vwa_chain_prepare refuses w_nt on a row-major weight); every other form returns -10 for it
 int vwa_chain_launch(const ChainParams* d_cp, int seq, int n_phases, int attn_g, int lds, int grid, hipStream_t st,
-                     int xg2 = 0, int f8 = 0, int o2 = 0, int n_layers = 1, int pk = 0);
+                     int xg2 = 0, int f8 = 0, int o2 = 0, int n_layers = 1, int pk = 0, int wa = 0);
 // -10: a shape / role table the kernel does not take (the caller keeps per-kernel launches)
 int vwa_wdec_launch(const WdecParams* p, int grid, hipStream_t st);
 int vwa_gemm(int epi, const GemmParams* p, hipStream_t st);

@@ -44,6 +44,9 @@ def main():
     ap.add_argument("--multi", type=int, default=0,
                     help="(--attn) also time N layers as ONE launch (chain_kernel MULTI; each layer its own K/V "
                          "cache, weights rotating over the copies): reports multi_layer_us = launch / N")
+    ap.add_argument("--wnt", default="0",
+                    help="(--attn, tiled) non-temporal weight stream (chain_make w_nt): 0 / 1, or a list such as 0,1,0,1 "
+                         "-- the measurements once per entry, in that order, in one process")
     a = ap.parse_args()
     if a.no_wait:
         a.bar_mode = 5 if a.bar_mode >= 4 else 3
@@ -116,138 +119,139 @@ def main():
     if a.attn and not a.no_plan:  # layers 1.. of a step: the plan layer 0 wrote (written once below)
         plan = dict(a_plan=torch.zeros(1024 * 16, dtype=torch.int32, device=dev), a_plan_mode=2)
 
-    def make(w, sc, pl):
-        return E.chain_make(h, att, act, wt(w, "o"), wt(w, "gu"), wt(w, "down"), 1e-5, wt(w, "qkv"), nq, nkv, hd, pos,
-                            slots, rope, q, kc, vc, bar, work, None if a.no_stamps else ts, a.bar_mode, **akw,
-                            w_tiled=a.tiled, **sc, **pl)
+    for wnt in [bool(int(x)) for x in a.wnt.split(",")]:  # (one record per entry, same weights and buffers)
+        def make(w, sc, pl):
+            return E.chain_make(h, att, act, wt(w, "o"), wt(w, "gu"), wt(w, "down"), 1e-5, wt(w, "qkv"), nq, nkv, hd, pos,
+                                slots, rope, q, kc, vc, bar, work, None if a.no_stamps else ts, a.bar_mode, **akw,
+                                w_tiled=a.tiled, **sc, **pl, w_nt=wnt)
 
-    descs = [make(w, sc, plan) for w, sc in zip(Ws, sck)]
-    if plan:
-        wdesc, wlds = make(Ws[0], sck[0], dict(plan, a_plan_mode=1))
-        E.chain_run(wdesc, 4, wlds, h, ag)
-    it = [0]
+        descs = [make(w, sc, plan) for w, sc in zip(Ws, sck)]
+        if plan:
+            wdesc, wlds = make(Ws[0], sck[0], dict(plan, a_plan_mode=1))
+            E.chain_run(wdesc, 4, wlds, h, ag)
+        it = [0]
 
-    def chained():
-        it[0] = (it[0] + 1) % ncopy
-        dsc, lds = descs[it[0]]
-        if a.warm_kv and a.attn:
-            ops.decode_attention(akw["a_q"], ops.KVLayout.paged(akw["a_k"], akw["a_v"], akw["a_table"]), akw["a_ctx"],
-                                 akw["a_seq"], n_q_heads=nq, n_kv_heads=nkv, head_dim=hd, scale=hd ** -0.5,
-                                 max_ctx=2048, out=akw["a_q"].new_empty(akw["a_q"].shape), part_o=akw["a_part_o"],
-                                 part_ml=akw["a_part_ml"], counters=akw["a_counters"])
-        E.chain_run(dsc, 4, lds, h, ag)
+        def chained():
+            it[0] = (it[0] + 1) % ncopy
+            dsc, lds = descs[it[0]]
+            if a.warm_kv and a.attn:
+                ops.decode_attention(akw["a_q"], ops.KVLayout.paged(akw["a_k"], akw["a_v"], akw["a_table"]), akw["a_ctx"],
+                                     akw["a_seq"], n_q_heads=nq, n_kv_heads=nkv, head_dim=hd, scale=hd ** -0.5,
+                                     max_ctx=2048, out=akw["a_q"].new_empty(akw["a_q"].shape), part_o=akw["a_part_o"],
+                                     part_ml=akw["a_part_ml"], counters=akw["a_counters"])
+            E.chain_run(dsc, 4, lds, h, ag)
 
-    def separate():
-        it[0] = (it[0] + 1) % ncopy
-        w = Ws[it[0]]
-        if a.attn:
-            ops.decode_attention(akw["a_q"], ops.KVLayout.paged(akw["a_k"], akw["a_v"], akw["a_table"]), akw["a_ctx"],
-                                 akw["a_seq"], n_q_heads=nq, n_kv_heads=nkv, head_dim=hd, scale=hd ** -0.5,
-                                 max_ctx=2048, out=att, part_o=akw["a_part_o"], part_ml=akw["a_part_ml"],
-                                 counters=akw["a_counters"])
-        ops.linear(att, w["o"], out=h, residual=h)
-        ops.linear_swiglu(h, w["gu"], fuse_rms=True, eps=1e-5, out=act)
-        ops.linear(act, w["down"], out=h, residual=h)
-        ops.qkv_rope_write(h, w["qkv"], None, fuse_rms=True, eps=1e-5, n_q_heads=nq, n_kv_heads=nkv, head_dim=hd,
-                           rope=rope, positions=pos, slots=slots, q_out=q, k_cache=kc, v_cache=vc)
+        def separate():
+            it[0] = (it[0] + 1) % ncopy
+            w = Ws[it[0]]
+            if a.attn:
+                ops.decode_attention(akw["a_q"], ops.KVLayout.paged(akw["a_k"], akw["a_v"], akw["a_table"]), akw["a_ctx"],
+                                     akw["a_seq"], n_q_heads=nq, n_kv_heads=nkv, head_dim=hd, scale=hd ** -0.5,
+                                     max_ctx=2048, out=att, part_o=akw["a_part_o"], part_ml=akw["a_part_ml"],
+                                     counters=akw["a_counters"])
+            ops.linear(att, w["o"], out=h, residual=h)
+            ops.linear_swiglu(h, w["gu"], fuse_rms=True, eps=1e-5, out=act)
+            ops.linear(act, w["down"], out=h, residual=h)
+            ops.qkv_rope_write(h, w["qkv"], None, fuse_rms=True, eps=1e-5, n_q_heads=nq, n_kv_heads=nkv, head_dim=hd,
+                               rope=rope, positions=pos, slots=slots, q_out=q, k_cache=kc, v_cache=vc)
 
-    multi_us = None
-    if a.multi > 1 and a.attn:
-        # N layers, layer i on weight copy i % ncopy and its own paged K/V (same table); layer 0
-        # writes the step plan, layers 1.. read it (as the engine's multi-layer launch)
-        mplan = torch.zeros(1024 * 16, dtype=torch.int32, device=dev)
-        kvs = [(torch.randn_like(akw["a_k"]) * 0.5, torch.randn_like(akw["a_v"])) for _ in range(a.multi + 1)]
-        mds = []
-        for li in range(a.multi):
-            w = Ws[li % ncopy]
-            kw = dict(akw, a_k=kvs[li][0], a_v=kvs[li][1])
-            mds.append(E.chain_make(h, att, act, wt(w, "o"), wt(w, "gu"), wt(w, "down"), 1e-5, wt(w, "qkv"), nq, nkv,
-                                    hd, pos, slots, rope, q, kvs[li + 1][0], kvs[li + 1][1], bar, work, None, a.bar_mode,
-                                    **kw, w_tiled=a.tiled, **sck[li % ncopy], a_plan=mplan,
-                                    a_plan_mode=1 if li == 0 else 2))
-        mcat = torch.cat([d[0] for d in mds])
-        mlds = mds[0][1]
+        multi_us = None
+        if a.multi > 1 and a.attn:
+            # N layers, layer i on weight copy i % ncopy and its own paged K/V (same table); layer 0
+            # writes the step plan, layers 1.. read it (as the engine's multi-layer launch)
+            mplan = torch.zeros(1024 * 16, dtype=torch.int32, device=dev)
+            kvs = [(torch.randn_like(akw["a_k"]) * 0.5, torch.randn_like(akw["a_v"])) for _ in range(a.multi + 1)]
+            mds = []
+            for li in range(a.multi):
+                w = Ws[li % ncopy]
+                kw = dict(akw, a_k=kvs[li][0], a_v=kvs[li][1])
+                mds.append(E.chain_make(h, att, act, wt(w, "o"), wt(w, "gu"), wt(w, "down"), 1e-5, wt(w, "qkv"), nq, nkv,
+                                        hd, pos, slots, rope, q, kvs[li + 1][0], kvs[li + 1][1], bar, work, None, a.bar_mode,
+                                        **kw, w_tiled=a.tiled, w_nt=wnt, **sck[li % ncopy], a_plan=mplan,
+                                        a_plan_mode=1 if li == 0 else 2))
+            mcat = torch.cat([d[0] for d in mds])
+            mlds = mds[0][1]
 
-        def multi():
-            E.chain_run(mcat, 4, mlds, h, ag, 0, a.multi)
+            def multi():
+                E.chain_run(mcat, 4, mlds, h, ag, 0, a.multi)
 
-        def per_layer():
-            for d in mds:
-                E.chain_run(d[0], 4, d[1], h, ag)
+            def per_layer():
+                for d in mds:
+                    E.chain_run(d[0], 4, d[1], h, ag)
 
-        multi()
+            multi()
+            torch.cuda.synchronize()
+            assert int(bar.view(torch.int64)[160].item()) == 0, "barrier timeout (multi)"
+            multi_us = timeit(multi) / a.multi
+            per_layer_us = timeit(per_layer) / a.multi
+            assert int(bar.view(torch.int64)[160].item()) == 0, "barrier timeout (multi)"
+        chained()  # one launch first: a broken barrier shows up as the error word, not a long run
         torch.cuda.synchronize()
-        assert int(bar.view(torch.int64)[160].item()) == 0, "barrier timeout (multi)"
-        multi_us = timeit(multi) / a.multi
-        per_layer_us = timeit(per_layer) / a.multi
-        assert int(bar.view(torch.int64)[160].item()) == 0, "barrier timeout (multi)"
-    chained()  # one launch first: a broken barrier shows up as the error word, not a long run
-    torch.cuda.synchronize()
-    assert int(bar.view(torch.int64)[160].item()) == 0, "barrier timeout"
-    t_sep = 0.0 if a.no_wait else timeit(separate)
-    t_ch = timeit(chained)
-    assert int(bar.view(torch.int64)[160].item()) == 0, "barrier timeout"
-    # stamps of the last launch: [start, end0, wait0, end1, wait1, end2, wait2, end3]
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
-    ns_ = 9 if a.attn else 8
-    st = ts.view(-1, 64)[:cus, :ns_].double().cpu()
-    st = (st - st[:, :1].min()) * 10e-3  # us
-    med = st.median(dim=0).values.tolist()
-    mx = st.max(dim=0).values.tolist()
-    mn = st.min(dim=0).values.tolist()
-    if a.attn:  # in-attention stamps 9..14 of the attention workgroups (slots stay 0 elsewhere)
-        full = ts.view(-1, 64)[:cus].double().cpu()
-        t0 = full[:, 0].min()
-        att = full[full[:, 9] > 0]
-        names = ["ctx_known", "q_ready", "pre_sync", "meta_landed", "kv_issue", "merged", "kv_landed", "meta_regs", "n_items", "loop_top", "ctxmax", "chunk_known", "pre_loop"]
-        extra = {}
-        for j, nm in enumerate(names):
-            col = att[:, 9 + j]
-            col = col[col > 0]
-            if col.numel():
-                extra[nm] = [round(float((col.median() - t0) * 10e-3), 2), round(float((col.max() - t0) * 10e-3), 2)]
-    r = dict(kernel="chain_probe", rows=M, plan=bool(plan), fp8=a.fp8, pack=a.pack,
-             pack_flagged=sum(p_.n_flagged for w in Ws for p_ in w.get("pk", {}).values()), ctx=a.ctx if a.attn else None, warm_kv=a.warm_kv, n_splits=a.n_splits, kv_tok_major=a.kv_tok_major, bar_mode=a.bar_mode, tiled=a.tiled, row_table=a.row_table, separate_us=round(t_sep, 2), chained_us=round(t_ch, 2),
-             stamps_med_us=[round(x, 2) for x in med], stamps_min_us=[round(x, 2) for x in mn],
-             stamps_max_us=[round(x, 2) for x in mx],
-             legend=("start,end_attn," if a.attn else "start,") + "end_o,wait_o,end_gu,wait_gu,end_down,wait_down,end_qkv")
-    if a.attn:
-        r["attn_stamps_med_max_us"] = extra
-        # phase stamps split by role: workgroups that ran an attention item vs the others
-        isatt = full[:, 9] > 0
-        for nm, sel in (("attn_wg", isatt), ("other_wg", ~isatt)):
-            if int(sel.sum()):
-                for slot, key in ((12, "meta_landed"), (56, "idle_issued")):
-                    col = full[sel, slot]
-                    col = col[col > t0]
-                    if col.numel():
-                        r[f"{nm}_{key}"] = [round(float((col.median() - t0) * 10e-3), 2),
-                                            round(float((col.max() - t0) * 10e-3), 2)]
-                s = st[sel]
-                r[nm] = dict(n=int(sel.sum()), med=[round(x, 2) for x in s.median(dim=0).values.tolist()],
-                             max=[round(x, 2) for x in s.max(dim=0).values.tolist()],
-                             argmax=[int(i) for i in torch.nonzero(sel).flatten()[s.argmax(dim=0)].tolist()])
-                # in-phase stamps (chain_phase pst): o_proj entry, X staged, scales, item0, fin0,
-                # item1, fin1 | gate/up entry, X staged, scales
-                ph = {}
-                # chain_phase pst: phase i at slots 22 + 8 i + k
-                kn = ["entry", "xstaged", "scales", "item0", "fin0", "item1", "fin1"]
-                for j, pn in [(8 * i + k, f"{pre}_{n}") for i, pre in enumerate(["o", "gu", "down", "qkv"])
-                              for k, n in enumerate(kn)]:
-                    col = full[sel, 22 + j]
-                    col = col[col > 0]
-                    if col.numel():
-                        ph[pn] = [round(float((col.median() - t0) * 10e-3), 2), round(float((col.max() - t0) * 10e-3), 2),
-                                  int(col.numel())]
-                r[nm + "_phase"] = ph
-    if multi_us is not None:
-        r.update(multi_layers=a.multi, multi_layer_us=round(multi_us, 2), per_layer_launch_us=round(per_layer_us, 2))
-    r["env"] = {k: v for k, v in os.environ.items() if k.startswith("VWA_CHAIN")}
-    r["layer_us"] = round(float(mx[-1]), 2)
-    print(json.dumps(r), flush=True)
-    if a.json:
-        with open(a.json, "a") as f:
-            f.write(json.dumps(r) + "\n")
+        assert int(bar.view(torch.int64)[160].item()) == 0, "barrier timeout"
+        t_sep = 0.0 if a.no_wait else timeit(separate)
+        t_ch = timeit(chained)
+        assert int(bar.view(torch.int64)[160].item()) == 0, "barrier timeout"
+        # stamps of the last launch: [start, end0, wait0, end1, wait1, end2, wait2, end3]
+        cus = torch.cuda.get_device_properties(0).multi_processor_count
+        ns_ = 9 if a.attn else 8
+        st = ts.view(-1, 64)[:cus, :ns_].double().cpu()
+        st = (st - st[:, :1].min()) * 10e-3  # us
+        med = st.median(dim=0).values.tolist()
+        mx = st.max(dim=0).values.tolist()
+        mn = st.min(dim=0).values.tolist()
+        if a.attn:  # in-attention stamps 9..14 of the attention workgroups (slots stay 0 elsewhere)
+            full = ts.view(-1, 64)[:cus].double().cpu()
+            t0 = full[:, 0].min()
+            awg = full[full[:, 9] > 0]  # (not `att`: the next --wnt entry's descriptors still need that tensor)
+            names = ["ctx_known", "q_ready", "pre_sync", "meta_landed", "kv_issue", "merged", "kv_landed", "meta_regs", "n_items", "loop_top", "ctxmax", "chunk_known", "pre_loop"]
+            extra = {}
+            for j, nm in enumerate(names):
+                col = awg[:, 9 + j]
+                col = col[col > 0]
+                if col.numel():
+                    extra[nm] = [round(float((col.median() - t0) * 10e-3), 2), round(float((col.max() - t0) * 10e-3), 2)]
+        r = dict(kernel="chain_probe", rows=M, plan=bool(plan), fp8=a.fp8, pack=a.pack, wnt=bool((descs[0][1] >> 29) & 1),
+                 pack_flagged=sum(p_.n_flagged for w in Ws for p_ in w.get("pk", {}).values()), ctx=a.ctx if a.attn else None, warm_kv=a.warm_kv, n_splits=a.n_splits, kv_tok_major=a.kv_tok_major, bar_mode=a.bar_mode, tiled=a.tiled, row_table=a.row_table, separate_us=round(t_sep, 2), chained_us=round(t_ch, 2),
+                 stamps_med_us=[round(x, 2) for x in med], stamps_min_us=[round(x, 2) for x in mn],
+                 stamps_max_us=[round(x, 2) for x in mx],
+                 legend=("start,end_attn," if a.attn else "start,") + "end_o,wait_o,end_gu,wait_gu,end_down,wait_down,end_qkv")
+        if a.attn:
+            r["attn_stamps_med_max_us"] = extra
+            # phase stamps split by role: workgroups that ran an attention item vs the others
+            isatt = full[:, 9] > 0
+            for nm, sel in (("attn_wg", isatt), ("other_wg", ~isatt)):
+                if int(sel.sum()):
+                    for slot, key in ((12, "meta_landed"), (56, "idle_issued")):
+                        col = full[sel, slot]
+                        col = col[col > t0]
+                        if col.numel():
+                            r[f"{nm}_{key}"] = [round(float((col.median() - t0) * 10e-3), 2),
+                                                round(float((col.max() - t0) * 10e-3), 2)]
+                    s = st[sel]
+                    r[nm] = dict(n=int(sel.sum()), med=[round(x, 2) for x in s.median(dim=0).values.tolist()],
+                                 max=[round(x, 2) for x in s.max(dim=0).values.tolist()],
+                                 argmax=[int(i) for i in torch.nonzero(sel).flatten()[s.argmax(dim=0)].tolist()])
+                    # in-phase stamps (chain_phase pst): o_proj entry, X staged, scales, item0, fin0,
+                    # item1, fin1 | gate/up entry, X staged, scales
+                    ph = {}
+                    # chain_phase pst: phase i at slots 22 + 8 i + k
+                    kn = ["entry", "xstaged", "scales", "item0", "fin0", "item1", "fin1"]
+                    for j, pn in [(8 * i + k, f"{pre}_{n}") for i, pre in enumerate(["o", "gu", "down", "qkv"])
+                                  for k, n in enumerate(kn)]:
+                        col = full[sel, 22 + j]
+                        col = col[col > 0]
+                        if col.numel():
+                            ph[pn] = [round(float((col.median() - t0) * 10e-3), 2), round(float((col.max() - t0) * 10e-3), 2),
+                                      int(col.numel())]
+                    r[nm + "_phase"] = ph
+        if multi_us is not None:
+            r.update(multi_layers=a.multi, multi_layer_us=round(multi_us, 2), per_layer_launch_us=round(per_layer_us, 2))
+        r["env"] = {k: v for k, v in os.environ.items() if k.startswith("VWA_CHAIN")}
+        r["layer_us"] = round(float(mx[-1]), 2)
+        print(json.dumps(r), flush=True)
+        if a.json:
+            with open(a.json, "a") as f:
+                f.write(json.dumps(r) + "\n")
 
 
 if __name__ == "__main__":

@@ -3,6 +3,7 @@ each), and batched admission prefill vs one prefill per request -- Llama-3-8B (o
 at the intent prompt's shape: a shared ~1k-token cached prefix + an ~85-token suffix per request.
 
     python tools/rows_sweep.py [--model llama3-8b] [--dtype bf16] [--rows 1,8,16,32,64] [--json out.jsonl]
+                               [--wnt 0,1,0,1]
 
 Per M: the step graph's replay (layers + all-rows LM head over the full vocab, like a decode
 iteration without the grammar mask) timed with HIP events over ITERS replays, each appending one
@@ -33,7 +34,12 @@ def main():
     ap.add_argument("--suffix", type=int, default=85)
     ap.add_argument("--json", default=None)
     ap.add_argument("--no-prefill-bench", action="store_true", help="skip the admission prefill comparison")
+    ap.add_argument("--wnt", default=None,
+                    help="non-temporal weight loads (VWA_CHAIN_WNT + VWA_STREAM_WNT): 0 / 1, or a list such as 0,1,0,1 -- "
+                         "the decode sweep once per entry, in that order, on the same model and engine (the step "
+                         "graphs are captured again for each); default: what the environment says")
     a = ap.parse_args()
+    wnt_list = [None] if a.wnt is None else [bool(int(x)) for x in a.wnt.split(",")]
     ops.ext()
     dev = torch.device("cuda")
     rows_list = [int(x) for x in a.rows.split(",")]
@@ -69,10 +75,21 @@ def main():
         for s in seqs:
             e.free_sequence(s, publish=False)
     # ---- decode step vs rows
-    seqs = [e.new_sequence(head + s) for s in suf]
-    e.prefill_batch([(s, len(s.tokens)) for s in seqs])
-    e.capture_all(buckets=tuple(b for b in BUCKETS if b <= R), logit_buckets=())
-    for M in rows_list:
+    seqs = []
+    for wnt, M in [(w, M) for w in wnt_list for M in rows_list]:
+        if M == rows_list[0]:
+            # every --wnt entry starts from the same context (each timed step appends a token per row,
+            # and the attention's share grows with it)
+            for s in seqs:
+                e.free_sequence(s, publish=False)
+            seqs = [e.new_sequence(head + s) for s in suf]
+            e.prefill_batch([(s, len(s.tokens)) for s in seqs])
+            if wnt is not None:  # the policy is part of the chain descriptors and of the captured graphs
+                os.environ["VWA_CHAIN_WNT"] = "1" if wnt else "0"
+                m.set_stream_nt(wnt)
+                m.reset_chains()
+                e.graphs.clear()
+            e.capture_all(buckets=tuple(b for b in BUCKETS if b <= R), logit_buckets=())
         rows = lambda: [(seqs[i], 7) for i in range(M)]  # noqa: E731
         for _ in range(3):
             e.run_rows(rows(), check=False)
@@ -101,6 +118,7 @@ def main():
             ts.append(ev[0].elapsed_time(ev[1]))
         full = sorted(ts)[len(ts) // 2]
         emit({"what": "decode_step", "model": a.model, "dtype": a.dtype, "rows": M, "chained": m._chain_ok(M),
+              "chain_wnt": ops.env_flag("VWA_CHAIN_WNT"), "stream_wnt": bool(getattr(m.lm_head, "nt", False)),
               "layers_ms": round(fwd, 3), "with_lm_head_ms": round(full, 3), "host_launch_us": round(host_us, 1),
               "weight_GB": round(m.weight_bytes() / 1e9, 2), "ctx": len(seqs[0].tokens)})
     if a.json:

@@ -85,6 +85,16 @@ class LlamaModel:
             raise ValueError(f"unsupported weight dtype {wdtype!r} (bf16 | fp8)")
         elif self.device.type == "cuda" and dtype == torch.bfloat16 and ops.env_flag("VWA_TILED_WEIGHTS"):
             self._tile_weights()
+        self.set_stream_nt(ops.env_flag("VWA_STREAM_WNT"))
+
+    def set_stream_nt(self, on: bool) -> None:
+        """VWA_STREAM_WNT: the <= 16-row streaming GEMMs (LM head, the 5..16-row steps' projections,
+        layer 0's QKV) load the pre-tiled layer and LM-head weights non-temporally -- a decode step
+        reads each of them once, from one CU, and 13-15 GB later nothing of it is left in a cache.
+        (The chained launch has its own switch, VWA_CHAIN_WNT, read when a descriptor is built.)"""
+        for w in [self.lm_head] + [t for L in self.layers for t in (L.qkv, L.o, L.gu, L.down)]:
+            if isinstance(w, ops.TiledWeight) or (isinstance(w, ops.FP8Weight) and w.tiled):
+                w.nt = bool(on)
 
     def _tile_weights(self) -> None:
         """Every projection + the LM head re-laid out ONCE into the pre-tiled MFMA-fragment order
@@ -340,6 +350,9 @@ class LlamaModel:
             pk = dict(p_o=L.o.pk.data, p_gu=L.gu.pk.data, p_down=L.down.pk.data, p_qkv=N.qkv.pk.data if nxt else None,
                       p_base=[w.pk.base for w in ws])
 
+        # VWA_CHAIN_WNT: non-temporal weight stream (the launch forms with the attention phase have it)
+        w_nt = bool(tiled and ops.env_flag("VWA_CHAIN_WNT"))
+
         def make(a):
             if a:
                 a = dict(a, **pk)
@@ -349,7 +362,7 @@ class LlamaModel:
                 bufs.positions if nxt else None, bufs.slots if nxt else None, self.rope if nxt else None,
                 bufs.q[:M] if nxt else None, kv.k[li + 1] if nxt else None, kv.v[li + 1] if nxt else None,
                 self._chain_bar, self._chain_work, None, self._chain_bar_mode, **a, w_tiled=tiled, **sc,
-                tp_ar=self.tp.custom_ar.state if self.tp.size > 1 else 0)
+                tp_ar=self.tp.custom_ar.state if self.tp.size > 1 else 0, w_nt=w_nt)
 
         desc, lds = make(a)
         if not desc.numel() and attn:

@@ -137,12 +137,13 @@ class FP8Weight:
     decode GEMMs (<= 16 rows) run the W8A8 streaming kernel (activations quantised per row on the
     fly, dynamic amax/448 scale, fp8 MFMA) and larger row counts the W8A8 tiled GEMM (gemm.hip F8,
     X quantised by one row-quantisation kernel).  The CPU reference emulates the same rounding.
+    ``nt`` (tiled only): the decode streaming GEMMs load it non-temporally (see TiledWeight.nt).
     """
 
-    __slots__ = ("w8", "scale", "tiled")
+    __slots__ = ("w8", "scale", "tiled", "nt")
 
-    def __init__(self, w8: torch.Tensor, scale: torch.Tensor, tiled: bool = False):
-        self.w8, self.scale, self.tiled = w8, scale, tiled
+    def __init__(self, w8: torch.Tensor, scale: torch.Tensor, tiled: bool = False, nt: bool = False):
+        self.w8, self.scale, self.tiled, self.nt = w8, scale, tiled, bool(nt and tiled)
 
     @staticmethod
     def quantize(w: torch.Tensor, tiled: Optional[bool] = None) -> "FP8Weight":
@@ -184,10 +185,10 @@ class FP8Weight:
         w8 = self.w8
         N, K = w8.shape
         if dev.type == "cuda" and not self.tiled and N % 16 == 0 and K % 128 == 0:
-            return FP8Weight(tile_weight_fp8(w8).to(dev), self.scale.to(dev), True)
+            return FP8Weight(tile_weight_fp8(w8).to(dev), self.scale.to(dev), True, self.nt)
         if dev.type == "cpu" and self.tiled:
             return FP8Weight(untile_weight_fp8(w8.to(dev)), self.scale.to(dev), False)
-        return FP8Weight(w8.to(dev), self.scale.to(dev), self.tiled)
+        return FP8Weight(w8.to(dev), self.scale.to(dev), self.tiled, self.nt)
 
 
 def quant_rows_fp8(x: torch.Tensor) -> torch.Tensor:
@@ -278,13 +279,19 @@ class TiledWeight:
     streaming / chained kernels (1 KB contiguous load instructions) and the LDS-tiled GEMM for
     prefill and > 16-row steps (gemm.hip copies the 4 KB fragment blocks to LDS verbatim) -- so
     the model keeps one copy of each weight.  ``dense()`` rebuilds the row-major matrix for the
-    CPU reference and diagnostics."""
+    CPU reference and diagnostics.
 
-    __slots__ = ("t", "pk")
+    ``nt``: the <= 16-row streaming GEMMs load this weight non-temporally (SkinnyParams::w_nt).  For
+    weights that one CU reads once per step and that are gone from the caches by the next step -- a
+    Llama layer's projections, the LM head (LlamaModel sets it, VWA_STREAM_WNT); never for a weight
+    that is replayed out of the cache from step to step (Whisper's decoder)."""
 
-    def __init__(self, w: Optional[torch.Tensor] = None, t: Optional[torch.Tensor] = None, pk=None):
+    __slots__ = ("t", "pk", "nt")
+
+    def __init__(self, w: Optional[torch.Tensor] = None, t: Optional[torch.Tensor] = None, pk=None, nt: bool = False):
         self.t = tile_weight(w) if t is None else t
         self.pk = pk  # optional PackedWeight of the same weight (the chained decode layer streams it)
+        self.nt = bool(nt)
 
     def dense(self) -> torch.Tensor:
         return untile_weight(self.t)
@@ -312,7 +319,7 @@ class TiledWeight:
         return self.t.element_size()
 
     def to(self, device) -> "TiledWeight":
-        return TiledWeight(t=self.t.to(device), pk=None if self.pk is None else self.pk.to(device))
+        return TiledWeight(t=self.t.to(device), pk=None if self.pk is None else self.pk.to(device), nt=self.nt)
 
 
 # ----------------------------------------------------------------------------- packed bf16 weights
@@ -720,7 +727,7 @@ def _linear_impl(x, w, bias, out, residual, act, fuse_rms, eps, out_dtype, ln_c,
                 assert act == "none"
                 epi = 1
             ext().skinny_gemm(x, w.t, bias, out, epi, fuse_rms and ln_c is None, eps, residual, None, ln_c, True,
-                              **mk)
+                              **mk, w_nt=w.nt)
             return out
         if ln_c is not None:
             return linear(_layernorm_plain(x, eps), w, bias, out=out, residual=residual, act=act, out_dtype=out_dtype)
@@ -747,7 +754,7 @@ def _linear_impl(x, w, bias, out, residual, act, fuse_rms, eps, out_dtype, ln_c,
             assert act == "none"
             epi = 1
         if fp8:
-            E.skinny_gemm(x, w.w8, bias, out, epi, fuse_rms, eps, residual, w.scale, None, w.tiled)
+            E.skinny_gemm(x, w.w8, bias, out, epi, fuse_rms, eps, residual, w.scale, None, w.tiled, w_nt=w.nt)
         else:
             E.skinny_gemm(x, w, bias, out, epi, fuse_rms, eps, residual, **mk)
         return out
@@ -788,7 +795,7 @@ def linear_swiglu(x: torch.Tensor, w_gu: torch.Tensor, *, fuse_rms: bool = False
         out = torch.empty((M, F), dtype=x.dtype, device=x.device)
     if isinstance(w_gu, TiledWeight):
         if _gpu(x) and _stream_ok(x, w_gu):
-            ext().skinny_gemm_swiglu(x, w_gu.t, None, out, fuse_rms, eps, None, True)
+            ext().skinny_gemm_swiglu(x, w_gu.t, None, out, fuse_rms, eps, None, True, w_gu.nt)
             return out
         if _gpu(x) and gemm_ok(x, w_gu, out):
             return gemm(x, w_gu, out, epi="swiglu", fuse_rms=fuse_rms, eps=eps, ss_in=ss_in)
@@ -800,7 +807,7 @@ def linear_swiglu(x: torch.Tensor, w_gu: torch.Tensor, *, fuse_rms: bool = False
     fp8 = isinstance(w_gu, FP8Weight)
     if M <= SKINNY_MAX_M and (not fp8 or _fp8_stream_fits(M, x.shape[1], nt=2)):
         if fp8:
-            E.skinny_gemm_swiglu(x, w_gu.w8, None, out, fuse_rms, eps, w_gu.scale, w_gu.tiled)
+            E.skinny_gemm_swiglu(x, w_gu.w8, None, out, fuse_rms, eps, w_gu.scale, w_gu.tiled, w_gu.nt)
         else:
             E.skinny_gemm_swiglu(x, w_gu, None, out, fuse_rms, eps)
         return out
@@ -856,7 +863,8 @@ def qkv_rope_write(x: torch.Tensor, w_qkv: torch.Tensor, bias: Optional[torch.Te
     if isinstance(w_qkv, TiledWeight):
         if _gpu(x) and _stream_ok(x, w_qkv) and (ln_c is None or _ln_fold_fits(x, w_qkv)):
             ext().skinny_gemm_qkv(x, w_qkv.t, bias, fuse_rms and ln_c is None, eps, n_q_heads, n_kv_heads, head_dim,
-                                  rope is not None, positions, slots, rope, q_out, k_cache, v_cache, None, ln_c, True)
+                                  rope is not None, positions, slots, rope, q_out, k_cache, v_cache, None, ln_c, True,
+                                  w_qkv.nt)
             return q_out[:M]
         if ln_c is not None:
             x, ln_c = _layernorm_plain(x, eps), None
@@ -899,7 +907,7 @@ def qkv_rope_write(x: torch.Tensor, w_qkv: torch.Tensor, bias: Optional[torch.Te
     if M <= SKINNY_MAX_M and (not fp8 or _fp8_stream_fits(M, x.shape[1])):
         if fp8:
             E.skinny_gemm_qkv(x, w_qkv.w8, bias, fuse_rms, eps, n_q_heads, n_kv_heads, head_dim, use_rope, positions,
-                              slots, rope, q_out, k_cache, v_cache, w_qkv.scale, None, w_qkv.tiled)
+                              slots, rope, q_out, k_cache, v_cache, w_qkv.scale, None, w_qkv.tiled, w_qkv.nt)
         else:
             E.skinny_gemm_qkv(x, w_qkv, bias, fuse_rms, eps, n_q_heads, n_kv_heads, head_dim, use_rope, positions,
                               slots, rope, q_out, k_cache, v_cache)

@@ -143,13 +143,15 @@ def build_native(force: bool = False) -> str:
 
 
 def build_all(force: bool = False) -> list[str]:
-    out = []
-    n = build_native(force)
-    if n:
-        out.append(n)
-    for sub, ext_name in KERNEL_LIBS:
-        out.append(_build_kernel_lib(sub, ext_name, force, 8))
-    return out
+    # the libraries build side by side: the main library's longest source (skinny_stream.hip, all the
+    # chained-layer instantiations in one translation unit) takes minutes on one core, and the six
+    # small libraries and the CPU runtime, a few minutes one after the other, fit beside it
+    with cf.ThreadPoolExecutor(max_workers=len(KERNEL_LIBS) + 1) as ex:
+        native = ex.submit(build_native, force)
+        libs = [ex.submit(_build_kernel_lib, sub, ext_name, force, 8 if i == 0 else 2)
+                for i, (sub, ext_name) in enumerate(KERNEL_LIBS)]
+        n = native.result()
+        return ([n] if n else []) + [f.result() for f in libs]
 
 
 if __name__ == "__main__":

@@ -156,6 +156,8 @@ class Settings(BaseModel):
     VWA_CHAIN_PLAN: bool = Field(True, description="chained attention: layer 0 writes the step's work plan, layers 1.. read it")
     VWA_CHAIN_MULTI: bool = Field(True, description="chained decode: all layers in ONE launch (skinny_stream.hip chain_kernel MULTI)")
     VWA_CHAIN_PACK: bool = Field(True, description="chained decode (bf16, one rank, <= 4 rows): stream a lossless 13-bit form of the layer weights (ops.pack_weight; 0.81 x the bytes, the same output bits) kept next to the tiled bf16 copy, about 0.8 x the layer weights' size in extra memory")
+    VWA_CHAIN_WNT: bool = Field(True, description="chained decode with the attention phase (packed, bf16, fp8): load the pre-tiled weight stream non-temporally (skinny_stream.hip chain_wnt_kernel; the same output bits)")
+    VWA_STREAM_WNT: bool = Field(True, description="Llama <= 16-row streaming GEMMs (LM head, 5..16-row steps): load the pre-tiled layer and LM-head weights non-temporally (SkinnyParams::w_nt; the same output bits)")
     VWA_CHAIN_BAR_MODE: int = Field(2, description="chained launches' grid barrier: 2 two-level tickets + scalar polls (default), 4 no-return arrivals + polled sum of the 8 group counters")
     VWA_CHAIN_SCHED: Optional[str] = Field(None, description="DIAGNOSTIC: chained schedule override name=value,...")
     VWA_GEMM_QKV: bool = Field(True, description="> 16-row QKV: rotary + KV write in the tiled GEMM epilogue")
