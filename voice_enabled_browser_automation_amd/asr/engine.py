@@ -19,11 +19,12 @@ from .. import ops
 from ..models.whisper import WhisperModel
 from ..tokenizer.languages import language_code, language_index, language_token
 from . import beam as beam_rule
+from .logit_steps import (TS_MAX_INITIAL, BoostBuffers, BoostRun, LogitSteps, ScoreBuffers,  # noqa: F401
+                          ScoreRun, TsBuffers, TsRun, ts_state)  # (TS_MAX_INITIAL, ts_state: also read from here)
 from .segments import segments
 from .words import Alignment, group_words
 
 BUCKETS = (1, 2, 4, 8, 16, 32, 64)
-
 
 
 class RunnerBuffers(SimpleNamespace):
@@ -160,319 +161,6 @@ class WhisperRunner:
         return out[:n]
 
 
-class BoostBuffers:
-    """The engine's keyterm boosting memory (built on the first boosted call): one int32 device
-    block of fixed size -- captured loop graphs address it -- and its pinned mirror,
-
-        roots [R] | state0 [R] | edge_off [CS + 1] | state_root [CS] | edge_tok | edge_next | edge_bias [CE each]
-
-    R = ops.BOOST_MAX_ROWS, CS / CE = ops.BOOST_CAP_STATES / BOOST_CAP_EDGES, plus two work state
-    rows.  Every launch covers all CS states and CE edges: states past those in use carry root -1 and
-    an empty list, so a stale state index becomes the row's root."""
-
-    def __init__(self, dev):
-        R, CS, CE = ops.BOOST_MAX_ROWS, ops.BOOST_CAP_STATES, ops.BOOST_CAP_EDGES
-        n = 2 * R + (CS + 1) + CS + 3 * CE
-        self.h = torch.zeros(n, dtype=torch.int32, pin_memory=dev.type == "cuda")
-        self.d = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.head = 2 * R
-        self.work = torch.zeros(2, R, dtype=torch.int32, device=dev)
-        self.key = None  # the automata the device tables hold (their keys, in table order; None: none)
-        self.bases: Dict[Tuple, int] = {}
-
-        def views(t):
-            o = 2 * R
-            parts = []
-            for m in (CS + 1, CS, CE, CE, CE):
-                parts.append(t[o : o + m])
-                o += m
-            off, root, tok, nxt, bias = parts
-            return t[:R], t[R : 2 * R], (off, tok, nxt, bias.view(torch.float32), root)
-
-        self.h_roots, self.h_state0, self.h_tables = views(self.h)
-        self.roots, self.state0, self.tables = views(self.d)
-
-
-class BoostRun:
-    """One decode_many call's keyterm boosting: which automaton each utterance has, where it sits in
-    the engine's tables, and the launches (ops.boost_step) in the three forms the decode paths use.
-    ``trace``: with AsrEngine.keep_boost_trace, one entry per launch."""
-
-    def __init__(self, bufs: BoostBuffers, sets: Sequence, vocab: int, trace: Optional[List[Dict]]):
-        from . import keyterms as kt
-
-        self.b = bufs
-        self.sets = list(sets)
-        self.vocab = vocab
-        self.trace = trace
-        distinct: Dict[Tuple, object] = {}
-        for ks in self.sets:
-            if ks is not None:
-                if not isinstance(ks, kt.KeytermSet):
-                    raise TypeError(f"keyterms: {type(ks).__name__} is not a compiled KeytermSet (asr/keyterms.py)")
-                distinct.setdefault(ks.key, ks)
-        S = sum(ks.n_states for ks in distinct.values())
-        E = sum(ks.n_edges for ks in distinct.values())
-        if S > ops.BOOST_CAP_STATES or E > ops.BOOST_CAP_EDGES:
-            raise RuntimeError(f"the call's {len(distinct)} keyterm automata hold {S} states / {E} edges: more than the "
-                               f"engine's tables ({ops.BOOST_CAP_STATES} / {ops.BOOST_CAP_EDGES})")
-        self.distinct = distinct
-        self.base: List[int] = []
-        self.cur = 0
-        self.n = 0
-        self.dirty = False
-
-    def load(self) -> None:
-        """Writes the call's tables into the pinned mirror when the device holds others (the copy
-        itself goes with the first ``stage``)."""
-        from . import keyterms as kt
-
-        keys = tuple(self.distinct)
-        b = self.b
-        if b.key != keys:
-            bases, off, tok, nxt, bias, root = kt.concat(list(self.distinct.values()))
-            h_off, h_tok, h_nxt, h_bias, h_root = b.h_tables
-            S, E = len(root), len(tok)
-            h_off.fill_(E)
-            h_off[: S + 1] = torch.from_numpy(off)
-            h_root.fill_(-1)
-            h_root[:S] = torch.from_numpy(root)
-            h_tok[:E] = torch.from_numpy(tok)
-            h_nxt[:E] = torch.from_numpy(nxt)
-            h_bias[:E] = torch.from_numpy(bias)
-            # (the device holds these only once stage() has queued the copy: until then it holds no
-            # set at all, so a call that fails in between leaves nothing a later call could trust)
-            b.key = None
-            b.bases = dict(zip(keys, bases))
-            self.dirty = True
-        self.keys = keys
-        self.base = [-1 if ks is None else b.bases[ks.key] for ks in self.sets]
-
-    def stage(self, utts: Sequence[int], hist: Sequence[Sequence[int]]) -> None:
-        """Row i is utterance utts[i] with text history hist[i]: its root and the state its
-        automaton is in after that history go to the device (with the tables, when they changed:
-        one copy either way)."""
-        b = self.b
-        self.n = n = len(utts)
-        assert 1 <= n <= ops.BOOST_MAX_ROWS
-        roots = [self.base[j] for j in utts]
-        b.h_roots.fill_(-1)
-        b.h_roots[:n] = torch.tensor(roots, dtype=torch.int32)
-        b.h_state0[:n] = torch.tensor([0 if r < 0 else r + self.sets[j].run(h) for r, j, h in zip(roots, utts, hist)],
-                                      dtype=torch.int32)
-        m = b.h.numel() if self.dirty else b.head
-        b.d[:m].copy_(b.h[:m], non_blocking=True)
-        if self.dirty:
-            b.key = self.keys
-        self.dirty = False
-        self.utts = list(utts)
-
-    def _launch(self, x: torch.Tensor, hist, state_in, state_out, **kw) -> None:
-        n = self.n
-        assert x.shape[0] == n
-        before = x.cpu().clone() if self.trace is not None else None
-        ops.boost_step(x, self.vocab, self.b.tables, self.b.roots[:n], state_in, state_out, **kw)
-        if self.trace is not None:
-            roots = [self.base[j] for j in self.utts]
-            self.trace.append(dict(utts=list(self.utts), history=[list(h) for h in hist], before=before,
-                                   after=x.cpu().clone(), sets=[self.sets[j] for j in self.utts],
-                                   state=[-1 if r < 0 else s - r for s, r in zip(state_out[:n].tolist(), roots)]))
-
-    def apply(self, x: torch.Tensor, hist) -> None:
-        """After ``stage``: the staged states' biases (no token to move on by)."""
-        self.cur = 0
-        self._launch(x, hist, self.b.state0, self.b.work[0])
-
-    def advance(self, x: torch.Tensor, tokens: torch.Tensor, hist) -> None:
-        """Every row moves on by its own last token, in place."""
-        w = self.b.work[self.cur]
-        self._launch(x, hist, w, w, tokens=tokens)
-
-    def follow(self, x: torch.Tensor, tokens: torch.Tensor, parents: torch.Tensor, W: int, hist) -> None:
-        """Beams: row r continues the state of its group's beam parents[r], then moves on by tokens[r]."""
-        self._launch(x, hist, self.b.work[self.cur], self.b.work[1 - self.cur], tokens=tokens, parents=parents, W=W)
-        self.cur = 1 - self.cur
-
-    def note(self, **kw) -> None:
-        if self.trace is not None and self.trace:
-            self.trace[-1].update(kw)
-
-
-TS_MAX_INITIAL = 50  # the first timestamp of a window may be at most 1.0 s (Whisper's max_initial_timestamp)
-
-
-class TsBuffers:
-    """The engine's timestamp rules memory (built on the first timestamp call): one int32 device
-    block of fixed size -- captured loop graphs address it -- and its pinned mirror,
-
-        enable [R] | state0 [R, 4]
-
-    R = ops.TS_MAX_ROWS, plus the work states [R, 4] the launches step in place."""
-
-    def __init__(self, dev):
-        R = ops.TS_MAX_ROWS
-        self.h = torch.zeros(5 * R, dtype=torch.int32, pin_memory=dev.type == "cuda")
-        self.d = torch.zeros(5 * R, dtype=torch.int32, device=dev)
-        self.work = torch.zeros(R, 4, dtype=torch.int32, device=dev)
-        self.h_enable, self.h_state0 = self.h[:R], self.h[R:].view(R, 4)
-        self.enable, self.state0 = self.d[:R], self.d[R:].view(R, 4)
-
-
-def ts_state(hist: Sequence[int], ts_begin: int) -> List[int]:
-    """The rules' state (n, last, prev, last_ts) after the sampled tokens ``hist`` (csrc/tsrules/tsrules.h)."""
-    n = len(hist)
-    return [min(n, 2), hist[-1] if n >= 1 else -1, hist[-2] if n >= 2 else -1,
-            next((t - ts_begin for t in reversed(hist) if t >= ts_begin), -1)]
-
-
-class TsRun:
-    """One decode_many call's timestamp rules: which utterances decode with timestamps, and the
-    launches (ops.ts_rules_step) in the two forms the greedy paths use.  ``trace``: with
-    AsrEngine.keep_ts_trace, one entry per launch."""
-
-    def __init__(self, bufs: TsBuffers, flags: Sequence[bool], cfg, trace: Optional[List[Dict]]):
-        self.b = bufs
-        self.flags = [bool(f) for f in flags]
-        self.vocab, self.eot, self.ts_begin = cfg.vocab_size, cfg.eot, cfg.no_timestamps + 1
-        self.trace = trace
-        self.n = 0
-        self.utts: List[int] = []
-
-    def stage(self, utts: Sequence[int], hist: Sequence[Sequence[int]]) -> None:
-        """Row i is utterance utts[i] with the sampled tokens hist[i]: whether the rules hold for it
-        and the state they are in after that history go to the device (one copy)."""
-        b = self.b
-        self.n = n = len(utts)
-        assert 1 <= n <= ops.TS_MAX_ROWS
-        b.h_enable.zero_()
-        b.h_enable[:n] = torch.tensor([int(self.flags[j]) for j in utts], dtype=torch.int32)
-        b.h_state0[:n] = torch.tensor([ts_state(h, self.ts_begin) for h in hist], dtype=torch.int32)
-        b.d.copy_(b.h, non_blocking=True)
-        self.utts = list(utts)
-
-    def _launch(self, x: torch.Tensor, mask: torch.Tensor, hist, state_in, state_out, tokens=None) -> None:
-        n = self.n
-        assert x.shape[0] == n
-        before = x.cpu().clone() if self.trace is not None else None
-        ops.ts_rules_step(x, self.vocab, self.eot, self.ts_begin, TS_MAX_INITIAL, mask, self.b.enable[:n], state_in,
-                          state_out, tokens=tokens)
-        if self.trace is not None:
-            self.trace.append(dict(utts=list(self.utts), history=[list(h) for h in hist], before=before,
-                                   after=x.cpu().clone(), enable=[self.flags[j] for j in self.utts],
-                                   mask=mask.cpu().clone(), state=state_out[:n].tolist()))
-
-    def apply(self, x: torch.Tensor, mask: torch.Tensor, hist) -> None:
-        """After ``stage``: the rules at the staged states (no token to move on by)."""
-        self._launch(x, mask, hist, self.b.state0, self.b.work)
-
-    def advance(self, x: torch.Tensor, mask: torch.Tensor, tokens: torch.Tensor, hist) -> None:
-        """Every row moves on by its own last token, in place."""
-        self._launch(x, mask, hist, self.b.work, self.b.work, tokens=tokens)
-
-    def note(self, **kw) -> None:
-        if self.trace is not None and self.trace:
-            self.trace[-1].update(kw)
-
-
-class ScoreBuffers:
-    """The engine's transcript score memory (built on the first scored call): one int32 device block
-    of fixed size -- captured loop graphs address it -- and its pinned mirror,
-
-        enable [R] | temperature [R] (f32) | sum0 [R] (f32) | cnt0 [R, 2]
-
-    R = ops.SCORE_MAX_ROWS, plus the work block the launches step in place and ONE device-to-host
-    copy reads:  sum [R] (f32) | cnt [R, 2] | step_lp [R] (f32)."""
-
-    def __init__(self, dev):
-        R = ops.SCORE_MAX_ROWS
-        f32 = torch.float32
-        self.h = torch.zeros(5 * R, dtype=torch.int32, pin_memory=dev.type == "cuda")
-        self.d = torch.zeros(5 * R, dtype=torch.int32, device=dev)
-        self.work = torch.zeros(4 * R, dtype=torch.int32, device=dev)
-
-        def views(t):
-            return t[:R], t[R : 2 * R].view(f32), t[2 * R : 3 * R].view(f32), t[3 * R :].view(R, 2)
-
-        self.h_enable, self.h_temp, self.h_sum0, self.h_cnt0 = views(self.h)
-        self.enable, self.temp, self.sum0, self.cnt0 = views(self.d)
-        w = self.work
-        self.sum, self.cnt, self.step_lp = w[:R].view(f32), w[R : 3 * R].view(R, 2), w[3 * R :].view(f32)
-
-
-class ScoreRun:
-    """One decode_many call's transcript scores: every utterance's temperature, the sums the host
-    holds (sum of log-probabilities, tokens counted, done), and the launches (ops.score_step) the
-    greedy paths make after each sampler launch.  ``trace``: with AsrEngine.keep_score_trace, one
-    entry per launch."""
-
-    def __init__(self, bufs: ScoreBuffers, B: int, cfg, trace: Optional[List[Dict]]):
-        self.b = bufs
-        self.vocab, self.eot = cfg.vocab_size, cfg.eot
-        self.trace = trace
-        self.temps = [0.0] * B          # this attempt's temperature, per utterance
-        self.sums = [0.0] * B           # the host's copy of every utterance's state
-        self.cnts = [[0, 0] for _ in range(B)]
-        self.attempt = 0
-        self.n = 0
-        self.utts: List[int] = []
-        self.fresh = False
-
-    def begin(self, utts: Sequence[int], temperatures: Sequence[float], attempt: int) -> None:
-        """A new attempt for ``utts`` at those temperatures: their sums start again."""
-        self.attempt = attempt
-        for j, t in zip(utts, temperatures):
-            self.temps[j], self.sums[j], self.cnts[j] = float(t), 0.0, [0, 0]
-        self.utts = []
-
-    def stage(self, utts: Sequence[int]) -> None:
-        """Row i is utterance utts[i]: its temperature and the state the host holds for it go to the
-        device (one copy); the next launch reads the staged state."""
-        b = self.b
-        self.n = n = len(utts)
-        assert 1 <= n <= ops.SCORE_MAX_ROWS
-        b.h_enable.zero_()
-        b.h_enable[:n] = 1
-        b.h_temp[:n] = torch.tensor([self.temps[j] for j in utts], dtype=torch.float32)
-        b.h_sum0[:n] = torch.tensor([self.sums[j] for j in utts], dtype=torch.float32)
-        b.h_cnt0[:n] = torch.tensor([self.cnts[j] for j in utts], dtype=torch.int32)
-        b.d.copy_(b.h, non_blocking=True)
-        self.utts = list(utts)
-        self.fresh = True
-
-    def temperature(self, n: int) -> torch.Tensor:
-        return self.b.temp[:n]
-
-    def step(self, x: torch.Tensor, mask: torch.Tensor, tokens: torch.Tensor, first: Optional[bool] = None) -> None:
-        """After the sampler wrote ``tokens``: every row's sum moves on by its token's log-probability
-        -- from the staged state (``first``; None: when ``stage`` ran since the last launch),
-        afterwards in place."""
-        b = self.b
-        n = self.n
-        assert x.shape[0] == n
-        first = self.fresh if first is None else first
-        self.fresh = False
-        si, ci = (b.sum0, b.cnt0) if first else (b.sum, b.cnt)
-        ops.score_step(x, self.vocab, self.eot, mask, b.enable[:n], tokens, si, b.sum, ci, b.cnt, step_lp=b.step_lp)
-        if self.trace is not None:
-            self.trace.append(dict(utts=list(self.utts), attempt=self.attempt, logits=x.cpu().clone(),
-                                   mask=mask.cpu().clone(), tokens=tokens[:n].tolist(),
-                                   temperature=[self.temps[j] for j in self.utts],
-                                   step_lp=b.step_lp[:n].tolist()))
-
-    def read(self) -> None:
-        """The staged rows' states come to the host (one copy of the work block)."""
-        if not self.utts or self.fresh:  # (nothing launched since the stage: the host's copy stands)
-            self.utts = []
-            return
-        R = ops.SCORE_MAX_ROWS
-        h = self.b.work.cpu()
-        sums = h[:R].view(torch.float32).tolist()
-        cnts = h[R : 3 * R].view(R, 2).tolist()
-        for i, j in enumerate(self.utts):
-            self.sums[j], self.cnts[j] = sums[i], cnts[i]
-        self.utts = []
-
-
 class AsrEngine:
     """Whisper transcription with fixed-work decoding options for benchmarking."""
 
@@ -579,8 +267,7 @@ class AsrEngine:
 
         return kt.compile_keyterms(terms, self.tok, self.model.cfg.eot, boost)
 
-    def _persistent_loop_ok(self, boost: Optional[BoostRun], ts: Optional[TsRun] = None,
-                            score: Optional[ScoreRun] = None) -> bool:
+    def _persistent_loop_ok(self, boost, ts=None, score=None) -> bool:
         """The one routing decision for the persistent one-launch decoder (wdec_loop_step): its
         argmax runs inside the kernel, before anything could bias or ban the logits, so a boosted
         call and a timestamp call never take it; nor does a scored call -- the logits never leave
@@ -622,69 +309,43 @@ class AsrEngine:
         t = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int16)).to(self.model.device, non_blocking=True)
         return ops.pcm16_to_f32(t, in_rate=rate)
 
-    def _sample(self, logits, allow_eot: bool, mask: Optional[torch.Tensor] = None,
-                temperature: Optional[torch.Tensor] = None) -> int:
-        ops.sample(logits, mask=self._mask(allow_eot) if mask is None else mask, temperature=temperature,
-                   seed=self.d_seed, step=self.d_step, out_tokens=self.d_tok, part_val=self.part_val,
-                   part_idx=self.part_idx)
-        return int(self.d_tok[0].item())
-
     # ---- device-resident greedy decode (one session): step graph = forward -> masked argmax ->
     # decode_advance (sampled token becomes the next input, position / context / KV slot move on),
     # replayed back to back; the host reads the tokens once per chunk instead of once per token
     # (measured per token before: 5 metadata copies + a host round trip, ~80 us of GPU idle)
-    def _loop_step(self, slot: int, allow_eot: bool, boost: Optional[BoostRun] = None,
-                   ts: Optional[TsRun] = None, score: Optional[ScoreRun] = None) -> None:
+    def _loop_step(self, slot: int, allow_eot: bool, steps: LogitSteps) -> None:
         r = self.runner
         b = r.b
         # whisper-large persistent decoder: embedding, layers, LM head, argmax and advance are ONE
         # launch (models/whisper.py wdec_loop_step)
-        if self._persistent_loop_ok(boost, ts, score) and self.model.wdec_loop_step(
+        if self._persistent_loop_ok(steps.boost, steps.ts, steps.score) and self.model.wdec_loop_step(
                 b, self.mask_text_eot if allow_eot else self.mask_text, self.d_tok, self.d_step, self.loop_out,
                 self.loop_cnt, 1 + slot * r.bps):
             return
         logits = r._fwd(1)
-        self._advance(logits, slot, allow_eot, boost, ts=ts, score=score)
+        self._advance(logits, slot, allow_eot, steps)
 
-    def _advance(self, logits: torch.Tensor, slot: int, allow_eot: bool, boost: Optional[BoostRun] = None,
-                 first: bool = False, ts: Optional[TsRun] = None, score: Optional[ScoreRun] = None) -> None:
-        """boost: the row's keyterm biases go onto the logits before the argmax reads them -- the
-        staged state's at the ``first`` step (after the prompt), afterwards the automaton moves on
-        by the token the previous step left in ``d_tok``, on the device (no host wait).  ts: the
-        timestamp rules follow in the same manner, on the biased logits.  score: the sampler reads
-        the row's temperature from the engine's fixed score buffers (0: the greedy path of
-        sample.hip, the same as no temperature at all), and the score launch follows it on the
-        logits it read, from the staged sums at the ``first`` step and in place afterwards."""
+    def _advance(self, logits: torch.Tensor, slot: int, allow_eot: bool, steps: LogitSteps, first=False) -> None:
+        """steps: the session's staged runs (row 0) launch around the sampler -- from the staged states
+        at the ``first`` step (after the prompt), afterwards moving on by the token the previous step
+        left in ``d_tok``, on the device (no host wait).  A scored sampler reads the row's temperature
+        from the score buffers (0: the greedy path of sample.hip, the same as no temperature at all)."""
         b = self.runner.b
-        if boost is not None:
-            if first:
-                boost.apply(logits[:1], ())
-            else:
-                boost.advance(logits[:1], self.d_tok, ())
-        mask = self._mask(allow_eot, ts is not None)
-        if ts is not None:
-            if first:
-                ts.apply(logits[:1], mask, ())
-            else:
-                ts.advance(logits[:1], mask, self.d_tok, ())
-        ops.sample(logits[:1], mask=mask, temperature=None if score is None else score.temperature(1),
-                   seed=self.d_seed, step=self.d_step, out_tokens=self.d_tok, part_val=self.part_val,
-                   part_idx=self.part_idx)
-        if score is not None:
-            score.step(logits[:1], mask, self.d_tok, first)
+        x = logits[:1]
+        mask, temperature = steps.before_sample(x, self.d_tok, allow_eot, first)
+        ops.sample(x, mask=mask, temperature=temperature, seed=self.d_seed, step=self.d_step, out_tokens=self.d_tok,
+                   part_val=self.part_val, part_idx=self.part_idx)
+        steps.after_sample(x, mask, self.d_tok, first)
         ops.ext().decode_advance(b.tokens, b.positions, b.ctx_lens, b.slots, self.d_tok, self.loop_out,
                                  self.loop_cnt, 1 + slot * self.runner.bps, self.runner.bs)
 
     LOOP_STEPS = 4  # decode steps per replayed loop graph (graph-to-graph launch gap ~10 us per replay)
 
-    def _loop_graph(self, slot: int, allow_eot: bool, steps: int = 1, boost: Optional[BoostRun] = None,
-                    ts: Optional[TsRun] = None, score: Optional[ScoreRun] = None) -> "torch.cuda.CUDAGraph":
-        # (a boosted loop is a graph of its own: it holds the boosting launch and not the persistent
-        # decoder; it addresses the engine's fixed boosting buffers, so it serves every boosted call.
-        # A timestamp loop likewise: the rules launch, the timestamp masks, the engine's fixed states.
-        # A scored loop likewise: the score launch and a sampler that reads the row's temperature from
-        # the engine's fixed score buffers, so one graph serves every attempt at every temperature)
-        key = (slot, allow_eot, steps, boost is not None, ts is not None) + ((True,) if score is not None else ())
+    def _loop_graph(self, slot: int, allow_eot: bool, steps: LogitSteps, n: int = 1) -> "torch.cuda.CUDAGraph":
+        # (a loop with boost, rules or score is a graph of its own: it holds those launches and not the
+        # persistent decoder; it addresses the engine's fixed buffers and masks -- a scored sampler reads
+        # the row's temperature there -- so one graph serves every such call, attempt and temperature)
+        key = (slot, allow_eot, n) + steps.graph_key
         g = self.loop_graphs.get(key)
         if g is None:
             r = self.runner
@@ -697,26 +358,24 @@ class AsrEngine:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                self._loop_step(slot, allow_eot, boost, ts, score)
+                self._loop_step(slot, allow_eot, steps)
             torch.cuda.current_stream().wait_stream(s)
             g = torch.cuda.CUDAGraph()
             if r.pool is None:
                 r.pool = torch.cuda.graph_pool_handle()
             with torch.cuda.graph(g, pool=r.pool):
-                for _ in range(steps):  # identical steps: each reads what the previous advanced
-                    self._loop_step(slot, allow_eot, boost, ts, score)
+                for _ in range(n):  # identical steps: each reads what the previous advanced
+                    self._loop_step(slot, allow_eot, steps)
             self.loop_graphs[key] = g
         return g
 
-    def _decode_device(self, slot: int, first_logits: torch.Tensor, n_max: int, exact: bool,
-                       P: Optional[int] = None, boost: Optional[BoostRun] = None,
-                       ts: Optional[TsRun] = None, score: Optional[ScoreRun] = None,
-                       step0: int = 0) -> List[int]:
+    def _decode_device(self, slot: int, first_logits: torch.Tensor, n_max: int, exact: bool, steps: LogitSteps,
+                       P: Optional[int] = None, step0: int = 0) -> List[int]:
         """P: the session's prompt length (SOT sequence + any forced prefix) -- the first sampled
-        token sits at position P.  boost: the session's staged keyterm run (row 0); the graphs'
-        warm-up step moves its work state, which the first advance sets again from the staged one.
-        score: the session's staged score run (row 0), likewise; the warm-up also moves the sampler's
-        step counter, which a scored call therefore sets (``step0``) once the graphs exist."""
+        token sits at position P.  steps: the session's staged runs (row 0); the graphs' warm-up
+        step moves their work states, which the first advance sets again from the staged ones.  It
+        also moves the sampler's step counter, which a scored call therefore sets (``step0``) once
+        the graphs exist."""
         cfg = self.model.cfg
         r = self.runner
         b = r.b
@@ -724,16 +383,16 @@ class AsrEngine:
         n_max = min(n_max, self.loop_out.numel(), r.bps * r.bs - P)
         if n_max <= 0:
             return []
-        g = self._loop_graph(slot, not exact, boost=boost, ts=ts, score=score)
+        g = self._loop_graph(slot, not exact, steps)
         K = self.LOOP_STEPS
-        gk = self._loop_graph(slot, not exact, K, boost=boost, ts=ts, score=score) if K > 1 else None
-        if score is not None:
+        gk = self._loop_graph(slot, not exact, steps, K) if K > 1 else None
+        if steps.score is not None:
             self.d_step.fill_(step0)
         # row 0 = this session at the last prompt position; the first advance moves it to P
         b.seq_ids[:1].fill_(slot)
         b.positions[:1].fill_(P - 1)
         self.loop_cnt.zero_()
-        self._advance(first_logits, slot, not exact, boost, first=True, ts=ts, score=score)
+        self._advance(first_logits, slot, not exact, steps, first=True)
         out: List[int] = []
         done = 1
         chunk = n_max if exact else 8
@@ -870,6 +529,93 @@ class AsrEngine:
         decoder: its logits never leave the kernel -- the same trade as boost and rules.  All off:
         nothing of the score library is loaded, allocated or launched."""
         t0 = time.perf_counter()
+        kw = dict(max_tokens=max_tokens, min_tokens=min_tokens, exact_tokens=exact_tokens, words=words,
+                  languages=languages, task=task, beam_size=beam_size, keyterms=keyterms, timestamps=timestamps,
+                  score=score, temperatures=temperatures, fallback=fallback)
+        c = self._call(audios, prefixes, **kw)
+        m, r, cfg, B, W, steps, outs = self.model, self.runner, self.model.cfg, c.B, c.W, c.steps, c.outs
+        c.slots = slots = [self.free_slots.pop() for _ in range(B)]
+        # beams: utterance i's beams sit in slots[i] (beam 0: prompt, encoder K/V, alignment) and W - 1 more
+        c.beam_slots = beam_slots = ([[s] + [self.free_slots.pop() for _ in range(W - 1)] for s in slots]
+                                     if W > 1 else None)
+        cross_saved = None
+        try:
+            if beam_slots is not None:
+                ct = r.b.cross_table
+                cross_saved = ct.clone()
+                extra = torch.tensor([s for bs_ in beam_slots for s in bs_[1:]], dtype=torch.long, device=ct.device)
+                first = torch.tensor([bs_[0] for bs_ in beam_slots for _ in bs_[1:]], dtype=torch.long, device=ct.device)
+                ct[extra] = ct[first]  # every beam reads the utterance's one cross K/V
+            mel = m.mel_batch(audios)
+            enc = m.encode(mel)
+            self.set_cross_batch(slots, enc)
+            t_enc = time.perf_counter()
+            # GPU-side decode time (prompt step + token loop): the host stamps above are taken when
+            # the encoder and the cross K/V projections are LAUNCHED, so decode_ms also holds
+            # whatever of them was still running; events bracket the decoder's own stream time
+            ev = None
+            if m.device.type == "cuda":
+                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                ev[0].record()
+            beam_ms = None
+            if steps.score is None:
+                beam_ms = self._decode_pass(c, list(range(B)), True)
+            else:
+                from . import fallback as fb
+
+                if c.policy is None:
+                    res = self._attempt(c, list(range(B)), None)
+                    scores = [fb.score_entry(s_, n_, c.temps[j], 1, tx) for j, (s_, n_, tx) in enumerate(res)]
+                else:
+                    scores = fb.run(lambda utts, T: self._attempt(c, utts, T), B, c.policy,
+                                    gated=lambda j: bool(c.sot_read[j]["gated"]))
+            retry = self._chain_failed()  # (results of a timed-out chained launch are invalid: redo)
+            t_end = time.perf_counter()
+            dec_gpu = None
+            if ev is not None:
+                ev[1].record()
+                ev[1].synchronize()  # (the tokens were read back: the stream is already there)
+                dec_gpu = ev[0].elapsed_time(ev[1])
+            self.last_stats = dict(encode_ms=(t_enc - t0) * 1e3, decode_ms=(t_end - t_enc) * 1e3,
+                                   decode_gpu_ms=dec_gpu, total_ms=(t_end - t0) * 1e3,
+                                   tokens=sum(len(o) for o in outs), batch=B,
+                                   prefix_tokens=sum(len(f) for f in c.forced))
+            if steps.boost is not None:
+                self.last_stats["boosted"] = sum(k is not None for k in keyterms)
+            if steps.ts is not None:
+                self.last_stats["timestamps"] = sum(c.ts_flags)
+            if steps.score is not None:
+                self.last_stats.update(scored=B, attempts=c.attempts, retried=c.retried)
+            if beam_slots is not None:
+                self.last_stats["beam_size"] = W
+                if beam_ms is not None:
+                    self.last_stats["beam_ms"] = beam_ms()
+            if not retry:
+                # (fills in the detected language tokens; a fallback call has read it after its first attempt)
+                self.last_sot = c.sot_read if c.sot_read is not None else self._read_sot(c.sot, c.langs, c.prompts)
+                if steps.score is not None:
+                    self.last_scores = scores
+                self.last_segments = [segments(o, cfg.no_timestamps + 1, cfg.eot, self.tok) if f else None
+                                      for o, f in zip(outs, c.ts_flags)]
+                if words:
+                    self.last_alignments = self._align(slots, audios, c.prompts, outs, c.exact, min_tokens)
+                    self.last_stats["align_ms"] = (time.perf_counter() - t_end) * 1e3
+                return outs
+        finally:
+            if beam_slots is None:
+                self.free_slots.extend(slots)
+            else:
+                if cross_saved is not None:
+                    r.b.cross_table.copy_(cross_saved)
+                # (in reverse: the free list is what it was before the call)
+                self.free_slots.extend(reversed(slots + [s for bs_ in beam_slots for s in bs_[1:]]))
+        return self.decode_many(audios, prefixes, **kw)
+
+    def _call(self, audios, prefixes, *, max_tokens, min_tokens, exact_tokens, words, languages, task, beam_size,
+              keyterms, timestamps, score, temperatures, fallback) -> SimpleNamespace:
+        """Every check of a decode_many call's arguments, and what the call then works on: its
+        prompts, forced prefixes, limits, flags and LogitSteps.  It raises before a slot is taken or
+        anything is launched; a feature's buffers are built here, on its first call."""
         m = self.model
         B = len(audios)
         W = int(beam_size)
@@ -880,9 +626,7 @@ class AsrEngine:
         if W > 1 and (B * W > len(self.free_slots) or B * W > ops.BEAM_MAX_ROWS):
             raise RuntimeError(f"{B} utterances of {W} beams exceed the {min(len(self.free_slots), ops.BEAM_MAX_ROWS)} "
                                "free ASR session slots")
-        policy = fallback
-        sc: Optional[ScoreRun] = None
-        temps = [0.0] * B
+        policy, sc, temps = fallback, None, [0.0] * B
         scored = bool(score) or temperatures is not None or policy is not None
         if scored:
             from .fallback import FallbackPolicy
@@ -904,8 +648,7 @@ class AsrEngine:
                 raise RuntimeError(f"{B} scored utterances exceed {ops.SCORE_MAX_ROWS} rows")
         prefixes = [list(p) for p in prefixes] if prefixes is not None else [[] for _ in range(B)]
         assert len(prefixes) == B
-        ts: Optional[TsRun] = None
-        ts_flags = [False] * B
+        ts, ts_flags = None, [False] * B
         if timestamps is not None and any(timestamps):
             if len(timestamps) != B:
                 raise ValueError(f"timestamps: {len(timestamps)} entries for {B} utterances")
@@ -943,9 +686,7 @@ class AsrEngine:
                 self.last_score_trace = []
             sc = ScoreRun(self._score_bufs, B, m.cfg, self.last_score_trace if self.keep_score_trace else None)
             self.d_seed.fill_(int(self.sample_seed))
-        r = self.runner
-        cap = r.bps * r.bs  # decoder positions per session
-        cfg = m.cfg
+        cfg, cap = m.cfg, self.runner.bps * self.runner.bs  # (cap: decoder positions per session)
         langs = [self.language if l is None else str(l).strip().lower()
                  for l in (languages if languages is not None else [None] * B)]
         assert len(langs) == B
@@ -957,219 +698,79 @@ class AsrEngine:
             heads = [h[:3] if f else h for h, f in zip(heads, ts_flags)]
         prompts = [h + p[: max(0, cap - len(h) - 1)] for h, p in zip(heads, prefixes)]
         forced = [p[len(h):] for h, p in zip(heads, prompts)]  # the text prefix each decoder really gets
-        probe = any(auto) or self.no_speech_threshold > 0.0 or self.keep_sot
-        sot = None
-        slots = [self.free_slots.pop() for _ in range(B)]
-        # beams: utterance i's beams sit in slots[i] (beam 0: prompt, encoder K/V, alignment) and W - 1 more
-        beam_slots = [[s] + [self.free_slots.pop() for _ in range(W - 1)] for s in slots] if W > 1 else None
-        cross_saved = None
-        retry = False
-        try:
-            if beam_slots is not None:
-                ct = r.b.cross_table
-                cross_saved = ct.clone()
-                extra = torch.tensor([s for bs_ in beam_slots for s in bs_[1:]], dtype=torch.long, device=ct.device)
-                first = torch.tensor([bs_[0] for bs_ in beam_slots for _ in bs_[1:]], dtype=torch.long, device=ct.device)
-                ct[extra] = ct[first]  # every beam reads the utterance's one cross K/V
-            mel = m.mel_batch(audios)
-            enc = m.encode(mel)
-            self.set_cross_batch(slots, enc)
-            t_enc = time.perf_counter()
-            # GPU-side decode time (prompt step + token loop): the host stamps above are taken when
-            # the encoder and the cross K/V projections are LAUNCHED, so decode_ms also holds
-            # whatever of them was still running; events bracket the decoder's own stream time
-            ev = None
-            if m.device.type == "cuda":
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
-            outs: List[List[int]] = [[] for _ in range(B)]
-            n_max = exact_tokens if exact_tokens is not None else max_tokens
-            pos = [len(p) for p in prompts]  # next position per session
-            limit = [min(n_max, cap - len(p)) for p in prompts]
-            beam_ms = None
+        n_max = exact_tokens if exact_tokens is not None else max_tokens
+        return SimpleNamespace(
+            B=B, W=W, policy=policy, temps=temps, ts_flags=ts_flags, langs=langs, auto=auto, prompts=prompts,
+            forced=forced, steps=LogitSteps(self._mask, forced, boost, ts, sc),
+            probe=any(auto) or self.no_speech_threshold > 0.0 or self.keep_sot, sot=None, sot_read=None,
+            n_max=n_max, min_tokens=min_tokens, exact=exact_tokens is not None, outs=[[] for _ in range(B)],
+            pos=[len(p) for p in prompts], limit=[min(n_max, cap - len(p)) for p in prompts], attempts=0, retried=0)
 
-            def decode_pass(utts: List[int], first_pass: bool, step0: int = 0):
-                """The prompt step and the token loop of the utterances ``utts`` (ascending; every
-                utterance of the call at the first pass, the rejected ones at a fallback pass), on
-                their own slots: the encoder's output and the cross K/V stay.  Fills ``outs``."""
-                nonlocal sot
-                sl, pr = [slots[j] for j in utts], [prompts[j] for j in utts]
-                if not (first_pass and probe):
-                    logits = self._prompt_logits(sl, pr)
-                elif not any(auto):
-                    # the SOT row's logits do not depend on the rows after it: the one prompt step serves
-                    logits, sot_logits = self._prompt_logits(sl, pr, first=True)
-                    sot = self._probe(sot_logits)
-                else:
-                    logits, sot = self._prompt_auto(sl, pr, auto)
-                live = list(utts)
-                ms = None
-                if sc is not None:
-                    self.d_step.fill_(step0)
-                if beam_slots is not None:
-                    res, ms = self._decode_beams(beam_slots, logits, pos, limit, n_max, min_tokens,
-                                                 exact_tokens is not None, boost, forced)
-                    outs[:] = res
-                    live = []
-                elif (B == 1 and self.device_loop and (exact_tokens is not None or min_tokens == 0) and n_max > 0
-                      and not (boost is not None and self.keep_boost_trace)  # (the trace steps from the host)
-                      and not (ts is not None and self.keep_ts_trace)
-                      and not (sc is not None and self.keep_score_trace)):
-                    if boost is not None:
-                        boost.stage([0], [forced[0]])
-                        logits = logits.contiguous()
-                    if ts is not None:
-                        ts.stage([0], [[]])
-                        logits = logits.contiguous()
-                    if sc is not None:
-                        sc.stage([0])
-                        logits = logits.contiguous()
-                    outs[0] = self._decode_device(slots[0], logits, limit[0], exact_tokens is not None, P=pos[0],
-                                                  boost=boost, ts=ts, score=sc, step0=step0)
-                    live = []
-                staged: Optional[List[int]] = None  # the live rows the device's boosting states are those of
-                ts_staged: Optional[List[int]] = None  # ... the device's timestamp states are those of
-                ts_masks: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # their masks, without / with EOT
-                sc_staged: Optional[List[int]] = None  # ... the device's score states are those of
-                for i in range(n_max if live else 0):
-                    allow_eot = exact_tokens is None and i >= min_tokens
-                    if boost is not None:
-                        # batched greedy rows: while the live set stands, every row's automaton moves on by
-                        # the token the sampler left on the device; when a row drops out the rows move up,
-                        # and the states are staged again from the histories the host has anyway
-                        logits = logits.contiguous()
-                        # (the histories are built only where they are read: to stage, or for the trace)
-                        hist = [forced[j] + outs[j] for j in live] if live != staged or boost.trace is not None else ()
-                        if live != staged:
-                            boost.stage(live, hist)
-                            boost.apply(logits, hist)
-                            staged = list(live)
-                        else:
-                            boost.advance(logits, self.d_tok, hist)
-                    mask = None
-                    if ts is not None:
-                        # the same scheme for the rules' states (the sampled tokens alone: such a row has no
-                        # prefix); every row brings its own mask, text rows the text mask
-                        logits = logits.contiguous()
-                        hist = [outs[j] for j in live] if live != ts_staged or ts.trace is not None else ()
-                        if live != ts_staged:
-                            ts_masks = tuple(torch.cat([self._mask(e, ts_flags[j]) for j in live]) for e in (False, True))
-                            mask = ts_masks[allow_eot]
-                            ts.stage(live, hist)
-                            ts.apply(logits, mask, hist)
-                            ts_staged = list(live)
-                        else:
-                            mask = ts_masks[allow_eot]
-                            ts.advance(logits, mask, self.d_tok, hist)
-                    temp = None
-                    if sc is not None:
-                        # the same scheme for the scores: when the rows have moved up, the sums the device
-                        # holds come to the host (one copy) and go back in the new order with the rows'
-                        # temperatures (one copy) -- before the sampler, which reads the temperatures
-                        logits = logits.contiguous()
-                        if live != sc_staged:
-                            sc.read()
-                            sc.stage(live)
-                            sc_staged = list(live)
-                        temp = sc.temperature(len(live))
-                    toks = self._sample_rows(logits, allow_eot, mask, temp)
-                    if sc is not None:  # (after the sampler, on the logits and the mask it read)
-                        sc.step(logits, self._mask(allow_eot) if mask is None else mask, self.d_tok)
-                    if boost is not None:
-                        boost.note(tokens=list(toks), allow_eot=allow_eot)
-                    if ts is not None:
-                        ts.note(tokens=list(toks), allow_eot=allow_eot)
-                    nxt = []
-                    for j, tok in zip(live, toks):
-                        if tok == m.cfg.eot or tok < 0:
-                            continue
-                        outs[j].append(tok)
-                        if len(outs[j]) < limit[j]:
-                            nxt.append(j)
-                    live = nxt
-                    if not live or i + 1 >= n_max:
-                        break
-                    logits = self.runner.step([(slots[j], outs[j][-1], pos[j] + len(outs[j]) - 1) for j in live])
-                if sc is not None:
-                    sc.read()
-                return ms
+    def _decode_pass(self, c: SimpleNamespace, utts: List[int], first_pass: bool, step0: int = 0):
+        """The prompt step and the token loop of the utterances ``utts`` of the call ``c`` (ascending;
+        every utterance at the first pass, the rejected ones at a fallback pass), on their own
+        slots: the encoder's output and the cross K/V stay.  Fills ``c.outs``."""
+        steps, outs, limit = c.steps, c.outs, c.limit
+        sl, pr = [c.slots[j] for j in utts], [c.prompts[j] for j in utts]
+        if not (first_pass and c.probe):
+            logits = self._prompt_logits(sl, pr)
+        elif not any(c.auto):
+            # the SOT row's logits do not depend on the rows after it: the one prompt step serves
+            logits, sot_logits = self._prompt_logits(sl, pr, first=True)
+            c.sot = self._probe(sot_logits)
+        else:
+            logits, c.sot = self._prompt_auto(sl, pr, c.auto)
+        live, ms = list(utts), None
+        if steps.score is not None:
+            self.d_step.fill_(step0)
+        if c.beam_slots is not None:
+            res, ms = self._decode_beams(c.beam_slots, logits, c.pos, limit, c.n_max, c.min_tokens, c.exact,
+                                         steps.boost, c.forced)
+            outs[:] = res
+            live = []
+        elif (c.B == 1 and self.device_loop and (c.exact or c.min_tokens == 0) and c.n_max > 0
+              and not steps.traced):  # (a trace steps from the host)
+            steps.restage([0], outs)
+            outs[0] = self._decode_device(c.slots[0], logits, limit[0], c.exact, steps, P=c.pos[0], step0=step0)
+            live = []
+        for i in range(c.n_max if live else 0):
+            allow_eot = not c.exact and i >= c.min_tokens
+            first = steps.restage(live, outs)
+            mask, temperature = steps.before_sample(logits, self.d_tok, allow_eot, first)
+            toks = self._sample_rows(logits, mask, temperature)
+            steps.after_sample(logits, mask, self.d_tok, first)
+            steps.note(tokens=list(toks), allow_eot=allow_eot)
+            nxt = []
+            for j, tok in zip(live, toks):
+                if tok == self.model.cfg.eot or tok < 0:
+                    continue
+                outs[j].append(tok)
+                if len(outs[j]) < limit[j]:
+                    nxt.append(j)
+            live = nxt
+            if not live or i + 1 >= c.n_max:
+                break
+            logits = self.runner.step([(c.slots[j], outs[j][-1], c.pos[j] + len(outs[j]) - 1) for j in live])
+        steps.finish()
+        return ms
 
-            sot_read = None
-            if sc is None:
-                beam_ms = decode_pass(list(range(B)), True)
-            else:
-                from . import fallback as fb
-
-                attempts = [0]
-                retried = [0]
-
-                def attempt(utts: List[int], T: Optional[float]):
-                    nonlocal sot_read
-                    k = attempts[0]
-                    attempts[0] += 1
-                    sc.begin(utts, [temps[j] if T is None else T for j in utts], k)
-                    for j in utts:
-                        outs[j] = []
-                    decode_pass(utts, k == 0, k << 16)
-                    if k == 0 and policy is not None:
-                        # (the gate's verdicts, and an auto session's detected language token in its prompt)
-                        sot_read = self._read_sot(sot, langs, prompts)
-                    if k > 0:
-                        retried[0] += len(utts)
-                    return [(sc.sums[j], len(outs[j]), self.tok.decode([t for t in outs[j] if t < cfg.eot]))
-                            for j in utts]
-
-                if policy is None:
-                    res = attempt(list(range(B)), None)
-                    scores = [fb.score_entry(s_, n_, temps[j], 1, tx) for j, (s_, n_, tx) in enumerate(res)]
-                else:
-                    scores = fb.run(attempt, B, policy, gated=lambda j: bool(sot_read[j]["gated"]))
-            if self._chain_failed():  # results of a timed-out chained launch are invalid: redo
-                retry = True
-            t_end = time.perf_counter()
-            dec_gpu = None
-            if ev is not None:
-                ev[1].record()
-                ev[1].synchronize()  # (the tokens were read back: the stream is already there)
-                dec_gpu = ev[0].elapsed_time(ev[1])
-            self.last_stats = dict(encode_ms=(t_enc - t0) * 1e3, decode_ms=(t_end - t_enc) * 1e3,
-                                   decode_gpu_ms=dec_gpu, total_ms=(t_end - t0) * 1e3,
-                                   tokens=sum(len(o) for o in outs), batch=B,
-                                   prefix_tokens=sum(len(f) for f in forced))
-            if boost is not None:
-                self.last_stats["boosted"] = sum(k is not None for k in keyterms)
-            if ts is not None:
-                self.last_stats["timestamps"] = sum(ts_flags)
-            if sc is not None:
-                self.last_stats.update(scored=B, attempts=attempts[0], retried=retried[0])
-            if beam_slots is not None:
-                self.last_stats["beam_size"] = W
-                if beam_ms is not None:
-                    self.last_stats["beam_ms"] = beam_ms()
-            if not retry:
-                # (fills in the detected language tokens; a fallback call has read it after its first attempt)
-                self.last_sot = sot_read if sot_read is not None else self._read_sot(sot, langs, prompts)
-                if sc is not None:
-                    self.last_scores = scores
-                self.last_segments = [segments(o, cfg.no_timestamps + 1, cfg.eot, self.tok) if f else None
-                                      for o, f in zip(outs, ts_flags)]
-                if words:
-                    self.last_alignments = self._align(slots, audios, prompts, outs, exact_tokens is not None,
-                                                       min_tokens)
-                    self.last_stats["align_ms"] = (time.perf_counter() - t_end) * 1e3
-                return outs
-        finally:
-            if beam_slots is None:
-                self.free_slots.extend(slots)
-            else:
-                if cross_saved is not None:
-                    r.b.cross_table.copy_(cross_saved)
-                # (in reverse: the free list is what it was before the call)
-                self.free_slots.extend(reversed(slots + [s for bs_ in beam_slots for s in bs_[1:]]))
-        return self.decode_many(audios, prefixes, max_tokens=max_tokens, min_tokens=min_tokens,
-                                exact_tokens=exact_tokens, words=words, languages=languages, task=task,
-                                beam_size=beam_size, keyterms=keyterms, timestamps=timestamps, score=score,
-                                temperatures=temperatures, fallback=fallback)
+    def _attempt(self, c: SimpleNamespace, utts: List[int], T: Optional[float]):
+        """One scored decode of the utterances ``utts`` at the temperature T (None: each its own):
+        (sum of log-probabilities, tokens, text) per utterance -- what asr/fallback.py run asks for."""
+        k = c.attempts
+        c.attempts += 1
+        sc = c.steps.score
+        sc.begin(utts, [c.temps[j] if T is None else T for j in utts], k)
+        for j in utts:
+            c.outs[j] = []
+        self._decode_pass(c, utts, k == 0, k << 16)
+        if k == 0 and c.policy is not None:
+            # (the gate's verdicts, and an auto session's detected language token in its prompt)
+            c.sot_read = self._read_sot(c.sot, c.langs, c.prompts)
+        if k > 0:
+            c.retried += len(utts)
+        eot = self.model.cfg.eot
+        return [(sc.sums[j], len(c.outs[j]), self.tok.decode([t for t in c.outs[j] if t < eot])) for j in utts]
 
     def _decode_beams(self, beam_slots: List[List[int]], logits: torch.Tensor, pos: List[int], limit: List[int],
                       n_max: int, min_tokens: int, exact: bool, boost: Optional[BoostRun] = None,
@@ -1251,7 +852,6 @@ class AsrEngine:
         self.last_beam_trace = trace
         t_a = mark()  # (the first select's bracket holds the first staging copy)
         _, _, cum_d, _, _ = stage(live, [[0] * W for _ in live], [0] * len(live)) if live else (None,) * 5
-        staged: Optional[List[int]] = None  # the live utterances the device's boosting states are those of
         par_d = tok_d = None
         for i in range(n_max):
             if not live:
@@ -1260,14 +860,11 @@ class AsrEngine:
             allow_eot = not exact and i >= min_tokens
             cs, cb, ct = (res[k * G * K : (k + 1) * G * K].view(G, K) for k in range(3))
             if boost is not None:
-                hist = ([forced[j] + states[j].tokens[w] for j in live for w in range(W)]
-                        if live != staged or boost.trace is not None else ())
-                if live != staged:
-                    boost.stage([j for j in live for _ in range(W)], hist)
-                    boost.apply(x, hist)
-                    staged = list(live)
+                if boost.restage([j for j in live for _ in range(W)],
+                                 lambda: [forced[j] + states[j].tokens[w] for j in live for w in range(W)]):
+                    boost.step(x, None, True)
                 else:
-                    boost.follow(x, tok_d, par_d.reshape(-1), W, hist)
+                    boost.follow(x, tok_d, par_d.reshape(-1), W)
                 boost.note(alive=[c != beam_rule.NEG_INF for j in live for c in states[j].cum], allow_eot=allow_eot)
             ops.beam_select(x, cum_d, self.mask_text_eot if allow_eot else self.mask_text, cfg.vocab_size, W,
                             cand_score=cs, cand_beam=cb.view(torch.int32), cand_tok=ct.view(torch.int32))
@@ -1547,19 +1144,18 @@ class AsrEngine:
         self.loop_graphs.clear()
         return True
 
-    def _sample_rows(self, logits: torch.Tensor, allow_eot: bool, mask: Optional[torch.Tensor] = None,
-                     temperature: Optional[torch.Tensor] = None) -> List[int]:
-        """mask: the rows' own allow-bits [n, words] (a call with timestamp rows); None: the text mask.
+    def _sample_rows(self, logits: torch.Tensor, mask: torch.Tensor, temperature: Optional[torch.Tensor]) -> List[int]:
+        """mask: the rows' own allow-bits [n, words] (a call with timestamp rows) or one shared row.
         temperature: the rows' temperatures, f32 [n] on the device (a scored call); None: greedy."""
         n = logits.shape[0]
-        if n == 1:
-            return [self._sample(logits, allow_eot, mask, temperature)]
-        logits = logits.contiguous()
-        if mask is None:
-            mask = self._mask(allow_eot).expand(n, -1).contiguous()
-        assert n <= self.d_tok.numel()  # (a step has at most max(BUCKETS) rows; d_tok is never replaced)
-        part_val = torch.empty(n * 64, dtype=torch.float32, device=logits.device)
-        part_idx = torch.empty(n * 64, dtype=torch.int32, device=logits.device)
+        part_val, part_idx = self.part_val, self.part_idx
+        if n > 1:
+            logits = logits.contiguous()
+            if mask.shape[0] == 1:
+                mask = mask.expand(n, -1).contiguous()
+            assert n <= self.d_tok.numel()  # (a step has at most max(BUCKETS) rows; d_tok is never replaced)
+            part_val = torch.empty(n * 64, dtype=torch.float32, device=logits.device)
+            part_idx = torch.empty(n * 64, dtype=torch.int32, device=logits.device)
         ops.sample(logits, mask=mask, temperature=temperature, seed=self.d_seed, step=self.d_step,
                    out_tokens=self.d_tok, part_val=part_val, part_idx=part_idx)
         return self.d_tok[:n].tolist()
