@@ -14,7 +14,12 @@ grammar-constrained decoding:
 * a character budget (``budget_chars``) guarantees the JSON can always be closed, so every
   request terminates with a schema-valid ParseResponse;
 * **continuous batching**: concurrent requests (voice sessions) decode together, one ragged
-  forward + one masked-sampling launch per iteration for all of them.
+  forward + one masked-sampling launch per iteration for all of them;
+* **turn probes** (``turn`` / ``turn_async`` / ``submit_turn``): a request of another kind that asks
+  how likely the transcript is a finished command.  Its prompt is the ``/parse`` prompt cut inside
+  the user turn's ``{"text":"...`` (prompt.turn_tail); it is prefilled behind the same cached prefix,
+  its last prompt token joins one ragged step, and the probability that the next token closes the
+  string is read off its logits row by one ``ops.set_logprob`` launch -- nothing is decoded.
 
 `FakeIntentEngine` is the test double (the reference mocks callLLMJSON with vi.spyOn,
 apps/brain/test/parse.test.ts:7-21).
@@ -34,7 +39,7 @@ import torch
 
 from .. import ops
 from ..grammar import CompiledGrammar, intent_grammar
-from .prompt import llama3_chat, messages_for
+from .prompt import llama3_chat, messages_for, turn_tail
 
 
 class IntentEngineError(RuntimeError):
@@ -63,6 +68,9 @@ class IntentRequest:
     error: Optional[BaseException] = None
     future: Any = None
     diag: Optional[str] = None
+    kind: str = "parse"                 # "turn": a turn-completion probe (no matcher, nothing sampled)
+    probe_text: Optional[str] = None
+    result: Optional[Dict[str, Any]] = None
 
     def stats(self, t_end: float) -> Dict[str, Any]:
         return dict(prompt_tokens=len(self.ids), cached_prefix_tokens=self.cached,
@@ -73,6 +81,12 @@ class IntentRequest:
 
 
 _TOK_PENDING = -0x7A7A7A7A  # never a token id nor the sampler's -1 failure code
+
+
+def end_set_ids(tokenizer) -> List[int]:
+    """The ids that close a JSON string -- the turn probe's end set: every non-special id whose
+    bytes begin with ``"`` (``token_bytes()`` gives special and unused ids no bytes)."""
+    return [i for i, b in enumerate(tokenizer.token_bytes()) if b[:1] == b'"']
 
 
 class LLMIntentEngine:
@@ -135,6 +149,15 @@ class LLMIntentEngine:
                            admit_prefill_ms=0.0)
         self._prefix_ids: Dict[str, List[int]] = {}
         self._head_len = 0
+        # turn probes: the ids that close a JSON string, as packed allow-bits (one shared row); one
+        # (log p, log-sum-exp) pair per probe row, read back through pinned memory after a stream
+        # synchronise; the traced-run record of the ASR logit steps (off by default)
+        self._end_set: Optional[torch.Tensor] = None
+        self.d_turn = torch.zeros(R, 2, dtype=torch.float32, device=dev)
+        self.h_turn = torch.zeros(R, 2, dtype=torch.float32, pin_memory=pin)
+        self.keep_turn_trace = False
+        self.last_turn_trace: List[Dict[str, Any]] = []
+        self.last_turn_stats: Dict[str, Any] = {}
         self.waiting: Deque[IntentRequest] = deque()
         self.active: List[IntentRequest] = []
         self._lock = threading.Lock()
@@ -144,7 +167,9 @@ class LLMIntentEngine:
 
     # ------------------------------------------------------------------ helpers
     def _encode_prompt(self, messages) -> List[int]:
-        head, tail = self.chat_format(messages)
+        return self._encode_head_tail(*self.chat_format(messages))
+
+    def _encode_head_tail(self, head: str, tail: str) -> List[int]:
         ids = self._prefix_ids.get(head)
         if ids is None:
             ids = self.tok.encode(head)
@@ -179,14 +204,18 @@ class LLMIntentEngine:
 
     def _admit_begin(self, r: IntentRequest) -> None:
         """Prompt -> sequence (prefix-cache match) + grammar matcher; the prefill is left to the
-        caller (batched over every request admitted in the same iteration)."""
+        caller (batched over every request admitted in the same iteration).  A turn probe has no
+        matcher and no budget: nothing of it is decoded."""
         eng = self.engine
         r.t_start = time.perf_counter()
-        r.ids = self._encode_prompt(r.messages)
-        r.matcher = self.grammar.matcher(self.budget_chars)
-        if r.matcher.min_completion() > self.budget_chars:
-            raise IntentEngineError(f"budget_chars={self.budget_chars} is below the shortest schema-valid "
-                                    f"answer ({r.matcher.min_completion()} chars)")
+        if r.kind == "turn":
+            r.ids = self._encode_head_tail(*turn_tail(r.probe_text, self.chat_format))
+        else:
+            r.ids = self._encode_prompt(r.messages)
+            r.matcher = self.grammar.matcher(self.budget_chars)
+            if r.matcher.min_completion() > self.budget_chars:
+                raise IntentEngineError(f"budget_chars={self.budget_chars} is below the shortest schema-valid "
+                                        f"answer ({r.matcher.min_completion()} chars)")
         r.seq = eng.new_sequence(r.ids)
         r.cached = r.seq.n_computed
         if r.cached >= len(r.ids):  # whole prompt cached: recompute its last token for logits
@@ -195,12 +224,13 @@ class LLMIntentEngine:
     def _admit_end(self, r: IntentRequest) -> None:
         r.t_first = time.perf_counter()
         r.feed = [r.ids[-1]]  # the last prompt token joins the batched step
-        self._jump_forward(r)
+        if r.kind != "turn":
+            self._jump_forward(r)
 
     def _finish(self, r: IntentRequest, error: Optional[BaseException] = None) -> None:
         r.done = True
         r.error = error
-        if error is None:
+        if error is None and r.kind != "turn":
             r.text = r.out.decode("utf-8")
         if r.seq is not None:
             # only the static system + few-shot prefix is shared across requests; the request's
@@ -208,10 +238,15 @@ class LLMIntentEngine:
             self.engine.free_sequence(r.seq, publish_upto=self._head_len)
             r.seq = None
         r.t_end = time.perf_counter()
-        self.last_stats = r.stats(r.t_end)
+        if r.kind == "turn":
+            if r.result is not None:
+                r.result["ms"] = (r.t_end - r.t_submit) * 1e3
+                self.last_turn_stats = r.result
+        else:
+            self.last_stats = r.stats(r.t_end)
         if r.future is not None:
             if error is None:
-                r.future.set_result(r.text)
+                r.future.set_result(r.result if r.kind == "turn" else r.text)
             else:
                 r.future.set_exception(error)
 
@@ -263,7 +298,14 @@ class LLMIntentEngine:
         # rows: each request's pending tokens; requests that do not fit wait one iteration, a
         # feed longer than the row cap is consumed in pieces (sampled once it is exhausted)
         rows, last, batch, budget = [], [], [], self.max_rows
-        for r in self.active:
+        # turn probes go after the sampled requests, rows and logits rows alike, and are never
+        # given to the sampler: the sampled requests' row indices, their mask rows and the
+        # sampler's step counter are what they would be without the probes
+        probes: List[IntentRequest] = []
+        order = self.active
+        if any(r.kind == "turn" for r in order):
+            order = [r for r in order if r.kind != "turn"] + [r for r in order if r.kind == "turn"]
+        for r in order:
             if not r.feed or budget <= 0:
                 continue
             take = r.feed[:budget]
@@ -274,12 +316,16 @@ class LLMIntentEngine:
             r.feed = r.feed[len(take):]
             if not r.feed:
                 last.append(len(rows) - 1)
-                batch.append(r)
+                (probes if r.kind == "turn" else batch).append(r)
         if not rows:
             return finished
         tm = self.timing
         t0 = time.perf_counter()
-        if last:
+        if last and not batch:
+            # probes only: no sampler runs, so no fail word reports a chained launch that timed out
+            # -- the step is verified (and, if need be, re-run) synchronously
+            self.engine.run_rows(rows, logits_for=last, check=True, defer_head=True)
+        elif last:
             self.engine.run_rows(rows, logits_for=last, check=False, defer_head=True)
         else:
             # only part of one long feed fits this iteration: its rows still have to reach the KV
@@ -290,24 +336,39 @@ class LLMIntentEngine:
         self.batch_stats["iterations"] += 1
         self.batch_stats["rows"] += len(rows)
         self.batch_stats["max_active"] = max(self.batch_stats["max_active"], len(self.active))
-        if not batch:
+        if not batch and not probes:
             return finished
-        n = len(batch)
+        n, p = len(batch), len(probes)
         for i, r in enumerate(batch):  # CPU grammar masks overlap the in-flight forward
             r.matcher.fill_mask(self.h_mask_np[i])
+        if p:
+            # a probe reads every column of its row: its mask row is all ones and counts in
+            # mask_rows, so the masked LM head skips no vocab tile (a skipped tile's logits are stale)
+            self.h_mask_np[n : n + p] = -1
         t2 = time.perf_counter()
         if not self.zero_copy:
-            self.d_mask[:n].copy_(self.h_mask[:n], non_blocking=True)
+            self.d_mask[: n + p].copy_(self.h_mask[: n + p], non_blocking=True)
         mask = self.h_mask if self.zero_copy else self.d_mask
         # the LM head under the same masks: only vocab tiles some row may sample are computed
-        logits = self.engine.head_logits(col_mask=mask if self.masked_head else None, mask_rows=n, gather=False)
-        toks = self._sample(logits, n, self.engine.step_fail_word())
-        self.engine.host_synced()  # the sampled tokens are back: the step's staging copy has run
+        logits = self.engine.head_logits(col_mask=mask if self.masked_head else None, mask_rows=n + p, gather=False)
+        if p:
+            self._probe_launch(logits, n, p)  # (before the sampler, on the same stream)
+        if n:
+            toks = self._sample(logits[:n], n, self.engine.step_fail_word())
+        else:  # probes only: no sampler launch, the sampler's step counter does not move
+            toks = []
+            self._t3 = time.perf_counter()
         if any(t == -2 for t in toks):
             # the forward's chained launch timed out at a grid barrier (tokens -2 from the
             # sampler's fail word): re-run the step on the per-kernel path and sample again
+            self.engine.host_synced()
             logits = self.engine.recover_step()
-            toks = self._sample(logits, n, None)
+            toks = self._sample(logits[:n], n, None)
+            if p:
+                self._probe_launch(logits, n, p)  # the probes too, from the re-run logits
+        if p:
+            self._probe_finish(probes, logits, n, finished)
+        self.engine.host_synced()  # the sampled tokens are back: the step's staging copy has run
         t4 = time.perf_counter()
         tm["mask_ms"] += (t2 - t1) * 1e3
         tm["sample_launch_ms"] += (self._t3 - t2) * 1e3
@@ -374,6 +435,86 @@ class LLMIntentEngine:
             toks = self.d_tok[:n].tolist()
         self._t3 = t3
         return toks
+
+    # ------------------------------------------------------------------ turn probes
+    def end_set_ids(self) -> List[int]:
+        return end_set_ids(self.tok)
+
+    def end_set(self) -> torch.Tensor:
+        """``end_set_ids`` as packed allow-bits, int32 [1, words], like the grammar masks and as
+        wide as the model's padded vocabulary; built once per engine (per tokenizer)."""
+        if self._end_set is None:
+            words = max(self.grammar.words, (self.engine.model.cfg.vocab_size + 31) // 32)
+            bits = np.zeros(words * 32, dtype=np.uint8)
+            bits[self.end_set_ids()] = 1
+            packed = np.packbits(bits, bitorder="little").view(np.int32).reshape(1, words)
+            self._end_set = torch.from_numpy(packed.copy()).to(self.dev)
+        return self._end_set
+
+    def _probe_launch(self, logits: torch.Tensor, n: int, p: int) -> None:
+        """One set_logprob launch over the probes' logits rows [n, n + p): (log p(end set), log-sum-exp)
+        per row into d_turn, and their copy to pinned memory, both on the step's stream."""
+        for i in range(0, p, ops.TURN_MAX_ROWS):
+            rows = logits[n + i : n + min(p, i + ops.TURN_MAX_ROWS)]
+            ops.set_logprob(rows, rows.shape[1], self.end_set(), out=self.d_turn[i : i + rows.shape[0]])
+        if self.dev.type == "cuda":
+            self.h_turn[:p].copy_(self.d_turn[:p], non_blocking=True)
+
+    def _probe_finish(self, probes: List[IntentRequest], logits: torch.Tensor, n: int,
+                      finished: List[IntentRequest]) -> None:
+        """Read the probes' results and retire them in this iteration.  The host reads only after the
+        stream is synchronised: seeing the sampler's tokens land (the pinned-buffer spin wait, the
+        zero-copy tokens) proves nothing about another kernel's output or its copy (the torn read
+        recorded at ``_sample``)."""
+        p = len(probes)
+        if self.dev.type == "cuda":
+            torch.cuda.current_stream().synchronize()
+            out = self.h_turn[:p].clone()
+        else:
+            out = self.d_turn[:p].clone()
+        for j, r in enumerate(probes):
+            lp = float(out[j, 0])
+            r.result = dict(p_end=float(np.exp(lp)), logprob=lp, prompt_tokens=len(r.ids),
+                            cached_prefix_tokens=r.cached, ms=0.0)
+            if self.keep_turn_trace:
+                self.last_turn_trace.append(dict(
+                    text=r.probe_text, ids=list(r.ids), row=n + j, logits=logits[n + j].detach().cpu().clone(),
+                    set=self.end_set().cpu().clone(), out=out[j].clone()))
+            self.batch_stats["probes"] = self.batch_stats.get("probes", 0) + 1
+            self._finish(r)  # frees the sequence; only the static head is published
+            finished.append(r)
+
+    def submit_turn(self, text: str, future=None) -> IntentRequest:
+        """Queue a turn-completion probe of ``text`` (admitted like any request)."""
+        if getattr(getattr(self.engine.model, "tp", None), "size", 1) > 1:
+            raise IntentEngineError("turn probes are not supported under tensor parallelism (vocab-parallel logits)")
+        if not isinstance(text, str):
+            raise IntentEngineError("turn: text must be a string")
+        r = IntentRequest(messages=[], t_submit=time.perf_counter(), future=future, kind="turn", probe_text=text)
+        with self._lock:
+            self.waiting.append(r)
+            self._wake.notify()
+        return r
+
+    def turn_async(self, text: str):
+        """concurrent.futures.Future resolved with the probe's dict (requires start())."""
+        fut: Future = Future()
+        self.submit_turn(text, future=fut)
+        return fut
+
+    def turn(self, text: str) -> Dict[str, Any]:
+        """How likely ``text`` is a finished command: ``{"p_end", "logprob", "prompt_tokens",
+        "cached_prefix_tokens", "ms"}`` -- the probability (and its log) that the token after
+        ``{"text":"<text>`` closes the string.  Through the background scheduler when it runs,
+        otherwise by stepping here."""
+        if self._thread is not None:
+            return self.turn_async(text).result()
+        r = self.submit_turn(text)
+        while not r.done:
+            self.step()
+        if r.error is not None:
+            raise r.error
+        return r.result
 
     def _diagnose(self, batch, toks, logits, n) -> None:
         """A -1 token means no admissible token had a finite logit: record what the row looked like

@@ -140,3 +140,30 @@ def plain_chat(messages: List[Dict[str, str]]) -> Tuple[str, str]:
 
 
 CHAT_FORMATS = {"llama3": llama3_chat, "plain": plain_chat}
+
+# what a recogniser may hang on a fragment ("search for." as readily as "scroll down."): stripped
+# before the turn probe asks whether the string closes, so that the period is not the answer
+TURN_TRAILING = ".?!,;:…"
+
+
+def turn_text(text: str) -> str:
+    """The transcript as the turn probe sees it: no surrounding whitespace, no trailing punctuation."""
+    return text.strip().rstrip(TURN_TRAILING + " \t\r\n\f\v").rstrip()
+
+
+def turn_tail(text: str, chat_format=llama3_chat) -> Tuple[str, str]:
+    """(static prefix, unfinished suffix) of the turn-completion probe: the ``/parse`` prompt of
+    ``{"text": t, "context": {}}`` -- the same static head, so one cached prefix serves both -- cut
+    right after the JSON-escaped ``t = turn_text(text)`` inside ``{"text":"``.  The few-shot user
+    turns before it are complete commands written the same way, so the model's probability that the
+    next token closes the string (begins with ``"``) is its belief that the command is finished.
+
+    The cut is made on the text, before tokenisation: where the vocabulary merges the last word
+    with the quote (``for"`` as one token), the full prompt's token boundary differs from the cut's
+    -- the probe then asks about ``for`` followed by a token that begins with ``"``, which is the
+    same string.  This token-boundary "healing" is accepted, not corrected."""
+    t = turn_text(text)
+    head, tail = chat_format(messages_for({"text": t, "context": {}}))
+    opening = '{"text":' + json.dumps(t, ensure_ascii=False)[:-1]
+    at = tail.index(opening)  # (the user turn's content starts with it: compact() writes "text" first)
+    return head, tail[: at + len(opening)]

@@ -1,4 +1,5 @@
-"""Brain service: ``GET /health``, ``POST /parse``, ``GET /metrics`` (parity with apps/brain/src/server.ts).
+"""Brain service: ``GET /health``, ``POST /parse``, ``GET /metrics`` (parity with apps/brain/src/server.ts),
+and ``POST /turn``, this project's own: the turn-completion probe.
 
 Request flow (apps/brain/src/server.ts:89-139):
   ParseRequest validation -> 400 {error:"invalid_request", detail}
@@ -7,6 +8,10 @@ Request flow (apps/brain/src/server.ts:89-139):
      reply fails ParseResponse -> ONE repair call with the repair system note
   final validation fails      -> 422 {error:"schema_validation_failed", detail}
   200 -> ParseResponse with zod-style defaults filled.
+
+``POST /turn`` {"text", "context"?}: 400 invalid_request for a missing, empty or non-string text;
+501 {error:"turn_unsupported"} for an engine without ``turn_async`` (keyword, TP); 500 llm_error as
+``/parse``; 200 {p_end, logprob, prompt_tokens, cached_prefix_tokens, ms}.
 
 With the LLM engine the grammar makes the first answer schema-valid, so the repair path only
 runs for engines without constrained decoding (or injected faults in tests).
@@ -111,10 +116,46 @@ def build_app(engine: Any = None) -> web.Application:
                 m.observe("decode_tok_per_s", toks / (st["decode_ms"] / 1e3))
         return web.json_response(final.data)
 
+    async def turn(req: web.Request) -> web.Response:
+        """How likely the transcript is a finished command (LLMIntentEngine.turn).  The probe reads
+        only the text: a ``context`` is accepted, as ``/parse`` clients send one, and ignored."""
+        m: Metrics = app["metrics"]
+        t0 = time.perf_counter()
+        try:
+            body = await req.json()
+        except Exception:  # noqa: BLE001
+            body = None
+        text = body.get("text") if isinstance(body, dict) else None
+        if not isinstance(text, str) or not text.strip() \
+                or not isinstance(body.get("context", {}), dict):
+            m.inc("invalid_request")
+            return web.json_response({"error": "invalid_request",
+                                      "detail": "body must be {\"text\": non-empty string, \"context\"?: object}"},
+                                     status=400)
+        eng = app["engine"]
+        if not hasattr(eng, "turn_async"):
+            m.inc("turn_unsupported")
+            return web.json_response({"error": "turn_unsupported"}, status=501)
+        try:
+            # a scheduler engine: the probe joins the running batch (no serial lock)
+            if hasattr(eng, "start"):
+                eng.start()
+            out = dict(await asyncio.wrap_future(eng.turn_async(text)))
+        except Exception as e:  # noqa: BLE001
+            m.inc("llm_error")
+            return web.json_response({"error": "llm_error", "detail": str(e) or e.__class__.__name__}, status=500)
+        for k in ("p_end", "logprob"):  # (JSON has no -inf: an end set at -inf reads p_end 0, logprob null)
+            if not isinstance(out.get(k), (int, float)) or out[k] != out[k] or out[k] in (float("inf"), float("-inf")):
+                out[k] = 0.0 if k == "p_end" else None
+        m.observe("turn_ms", (time.perf_counter() - t0) * 1e3)
+        m.inc("turn_ok")
+        return web.json_response(out)
+
     app.on_cleanup.append(on_cleanup)
     app.router.add_get("/health", health)
     app.router.add_get("/metrics", metrics)
     app.router.add_post("/parse", parse)
+    app.router.add_post("/turn", turn)
     return app
 
 

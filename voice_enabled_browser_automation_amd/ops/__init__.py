@@ -1788,3 +1788,58 @@ def score_step(logits: torch.Tensor, vocab: int, eot: int, mask: torch.Tensor, e
     # (a missing library raises: there is no other GPU path)
     score_ext().score_step(logits, vocab, eot, mask, enable, tokens, sum_in, sum_out, cnt_in, cnt_out, step_lp)
     return sum_out
+
+
+# ----------------------------------------------------------------------------- set log-probability
+TURN_MAX_ROWS = 64           # csrc/turn/turn.h kTurnMaxRows: rows per launch
+TURN_MAX_VOCAB = 1 << 20     # ... kTurnMaxVocab
+
+
+def turn_ext():
+    """The set log-probability library ``_vwa_turn.so`` (loaded once). Raises if unavailable."""
+    return _load_lib("_vwa_turn", "set log-probability")
+
+
+def set_logprob(logits: torch.Tensor, vocab: int, sets: torch.Tensor, *,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per row of f32 ``logits`` [rows <= 64, >= vocab], the log of the softmax mass (over the ids
+    below ``vocab``) that falls on a set of ids (csrc/turn/turn.h has the per-row rule): ``sets`` is
+    the set as packed allow-bits in the sampler's mask format, int32 [1 or >= rows, >= ceil(vocab /
+    32)] (one row: shared).  Returns ``out`` f32 [rows, 2] = (log p(set), log-sum-exp of the row):
+    -inf for an empty set, a set at -inf or a row at -inf, never NaN and never above 0.  The logits
+    are only read.  One launch on the GPU; host tensors take the Python reference and never load
+    the library."""
+    i32, f32, dev = torch.int32, torch.float32, logits.device
+    if logits.dim() != 2 or logits.dtype != f32 or logits.stride(1) != 1 \
+            or not (logits.shape[0] == 1 or logits.stride(0) >= logits.shape[1]) \
+            or not 1 <= logits.shape[0] <= TURN_MAX_ROWS:
+        raise ValueError(f"set_logprob: logits must be float32 [1..{TURN_MAX_ROWS}, >= vocab] with contiguous rows "
+                         f"that do not overlap, not {logits.dtype} {tuple(logits.shape)}")
+    rows = logits.shape[0]
+    vocab = int(vocab)
+    if not 1 <= vocab <= min(logits.shape[1], TURN_MAX_VOCAB):
+        raise ValueError(f"set_logprob: vocab = {vocab} outside [1, {min(logits.shape[1], TURN_MAX_VOCAB)}] (the logits' "
+                         "row length)")
+    words = (vocab + 31) // 32
+    if sets.dim() != 2 or sets.dtype != i32 or sets.stride(1) != 1 or sets.shape[1] < words \
+            or not (sets.shape[0] == 1 or (sets.shape[0] >= rows and sets.stride(0) >= sets.shape[1])):
+        raise ValueError(f"set_logprob: sets must be int32 [1 or >= {rows}, >= {words}] with contiguous rows that do "
+                         f"not overlap, not {sets.dtype} {tuple(sets.shape)}")
+    if out is None:
+        out = torch.empty(rows, 2, dtype=f32, device=dev)
+    if out.dim() != 2 or out.dtype != f32 or not out.is_contiguous() or tuple(out.shape) != (rows, 2):
+        raise ValueError(f"set_logprob: out must be contiguous float32 [{rows}, 2], not {out.dtype} {tuple(out.shape)}")
+    for name, t in (("sets", sets), ("out", out)):
+        if t.device != dev:
+            raise ValueError(f"set_logprob: {name} is on {t.device}, the logits on {dev}")
+    o = out.data_ptr()
+    for name, t, nb in (("logits", logits, 4 * ((rows - 1) * logits.stride(0) + vocab)),
+                        ("sets", sets, 4 * ((rows - 1) * (sets.stride(0) if sets.shape[0] > 1 else 0) + words))):
+        a = t.data_ptr()
+        if o < a + nb and a < o + 8 * rows:
+            raise ValueError(f"set_logprob: out must not overlap {name}")
+    if not _gpu(logits):
+        return ref.set_logprob(logits, vocab, sets, out)
+    # (a missing library raises: there is no other GPU path)
+    turn_ext().set_logprob(logits, vocab, sets, out)
+    return out

@@ -642,3 +642,20 @@ def score_step(logits, vocab, eot, mask, enable, tokens, sum_in, sum_out, cnt_in
         if step_lp is not None:
             step_lp[r] = lp32
     return sum_out, cnt_out
+
+
+def set_logprob(logits, vocab, sets, out):
+    """The set log-probability on host tensors, as csrc/turn/turn.h states it (both log-sum-exps in
+    f64, rounded to f32 once)."""
+    ninf = float("-inf")
+    ids = torch.arange(vocab)
+    for r in range(logits.shape[0]):
+        s = sets[r if sets.shape[0] > 1 else 0]
+        on = ((s[ids >> 5] >> (ids & 31)) & 1).bool()
+        x = logits[r, :vocab].double()
+        live = x > ninf  # (False for a NaN too)
+        A = float(torch.logsumexp(x[live], 0)) if bool(live.any()) else ninf
+        hit = live & on
+        out[r, 0] = min(float(torch.logsumexp(x[hit], 0)) - A, 0.0) if bool(hit.any()) else ninf
+        out[r, 1] = A
+    return out

@@ -105,6 +105,10 @@ class Settings(BaseModel):
     VWA_DEBOUNCE_MS: float = Field(1000.0, description="final transcript -> brain call debounce (reference: 1000)")
     VWA_COMMIT_MS: float = Field(0.0, description="voice: silence after the speech end before pending finals are a command (0: the ASR endpoint; speech resuming earlier holds them -- voice/server.py commit policy)")
     VWA_SPEC_BRAIN: bool = Field(True, description="voice: start the brain on the ASR's speculative final pass (its answer is used only for exactly that text)")
+    VWA_TURN: bool = Field(False, description="voice: ask the brain's turn-completion probe (POST /turn) whether the pending text is a finished command and, if it says so, commit without waiting out VWA_COMMIT_MS (0, the default: no request is ever made to /turn and every timing is the fixed timer's)")
+    VWA_TURN_URL: Optional[str] = Field(None, description="voice -> brain /turn URL (default: BRAIN_URL with /parse replaced by /turn)")
+    VWA_TURN_THRESHOLD: float = Field(0.5, gt=0.0, le=1.0, description="voice: a pending text whose probe answers p_end >= this is a finished command. In (0, 1]; 1.0 never commits early. 0.5 is a policy default and is NOT tuned on real speech or real weights")
+    VWA_COMMIT_MIN_MS: float = Field(0.0, ge=0.0, description="voice: silence after the speech end before a command the turn probe judged complete is committed (0: as soon as the verdict and the ASR final are both there)")
     VWA_ASR_BUSY_FILE: Optional[str] = Field(None, description="/dev/shm word the voice worker's ASR batcher marks busy while recognition runs (shared-GPU deployment: the brain's decode uses the chained launch only while it is idle; launch.py sets it)")
     VWA_ASR_BUSY_HOLD_MS: float = Field(20.0, description="brain: keep the per-kernel decode form this long after the last ASR pass ended")
     VWA_ENDPOINT_MS: float = Field(300.0, description="trailing silence that ends an utterance (VAD endpoint)")

@@ -13,6 +13,15 @@ Per connection:
     speculative final pass (``VWA_SPEC_BRAIN``), so its latency hides in the endpoint / commit
     wait, and its answer is used only if the committed text is exactly the text it parsed (and
     the context did not change meanwhile) -- otherwise it is dropped and the merged text parsed;
+  * turn-completion probe (``VWA_TURN``, off by default): a fixed silence timer cannot tell "search
+    for" + pause from "scroll down" + pause; the brain can (``POST /turn``: the probability that the
+    pending text is a finished command).  The connection asks on the speculative final pass and,
+    if it then has no verdict for exactly the pending text, on the committing final.  The final
+    arms the full hold as ever; a verdict ``p_end >= VWA_TURN_THRESHOLD`` for exactly the pending
+    text, arriving while that commit is still armed, re-arms it to ``VWA_COMMIT_MIN_MS`` after the
+    speech end (not before the debounce).  Anything else -- a lower ``p_end``, an HTTP error,
+    garbage, no answer yet, another text -- leaves the full window standing, and ``SpeechStarted``
+    cancels as before whatever the verdict was;
   * brain reply -> ``intent`` frame, ``tts`` frame (tts_summary), context merge of
     ``context_updates``, safe/risky split: safe intents go to ``POST EXECUTOR_URL/execute`` with
     the connection's executor session id (``execution_result`` / ``execution_error``), risky
@@ -136,7 +145,9 @@ async def post_json_and_return(session: aiohttp.ClientSession, url: str, body: A
 
 def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Optional[str] = None,
               executor_url: Optional[str] = None, debounce_ms: Optional[float] = None,
-              commit_ms: Optional[float] = None, spec_brain: Optional[bool] = None) -> web.Application:
+              commit_ms: Optional[float] = None, spec_brain: Optional[bool] = None, turn: Optional[bool] = None,
+              turn_url: Optional[str] = None, turn_threshold: Optional[float] = None,
+              commit_min_ms: Optional[float] = None) -> web.Application:
     """asr_factory() -> a StreamingAsrSession-like object (push(bytes)->events, flush()->events);
     None = passthrough mode (no recognizer, as the reference without DEEPGRAM_API_KEY)."""
     app = web.Application()
@@ -157,6 +168,21 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
     spec_brain = knob("VWA_SPEC_BRAIN") if spec_brain is None else spec_brain
     # the ASR final fires endpoint_ms after the speech end: the commit window's rest comes after it
     hold_s = max(debounce_ms, commit_ms - knob("VWA_ENDPOINT_MS")) / 1000.0
+    # turn-completion probe (module docstring): off unless VWA_TURN; the hold of a command it judged complete
+    turn_on = bool(knob("VWA_TURN") if turn is None else turn)
+    if turn_url is None:
+        turn_url = knob("VWA_TURN_URL")
+    if not turn_url:
+        base, sep, rest = brain_url.rpartition("/parse")
+        turn_url = base + "/turn" + rest if sep else brain_url.rstrip("/") + "/turn"
+    turn_threshold = float(knob("VWA_TURN_THRESHOLD") if turn_threshold is None else turn_threshold)
+    if not 0.0 < turn_threshold <= 1.0:
+        raise ValueError(f"turn_threshold = {turn_threshold} outside (0, 1]")
+    commit_min_ms = float(knob("VWA_COMMIT_MIN_MS") if commit_min_ms is None else commit_min_ms)
+    if commit_min_ms < 0:
+        raise ValueError(f"commit_min_ms = {commit_min_ms} is negative")
+    early_s = max(debounce_ms, commit_min_ms - knob("VWA_ENDPOINT_MS")) / 1000.0
+    turn_state = {"unsupported": False}  # set by the brain's first 501: the app stops asking
 
     async def on_startup(app_):
         app_["http"] = aiohttp.ClientSession(timeout=aiohttp.ClientTimeout(total=120))
@@ -192,7 +218,8 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
         # pending: final text not yet sent to the brain; spec: a speculative brain call {text, ctx,
         # task}; ctx: context version (a speculative answer is only used for the context it saw)
         st: Dict[str, Any] = {"context": {}, "pending": "", "debounce": None, "session_id": None, "closed": False,
-                              "t_final": None, "t_utt": None, "spec": None, "ctx": 0, "procs": set()}
+                              "t_final": None, "t_utt": None, "spec": None, "ctx": 0, "procs": set(),
+                              "turn": None}  # turn: the latest probe {text, task, done, complete}
         lock = asyncio.Lock()
 
         async def send(obj):
@@ -369,30 +396,92 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
                         await send({"type": "confirmation_required",
                                     "payload": f"{len(risky)} risky actions require manual confirmation"})
 
-        async def debounced():
+        async def debounced(delay: float = hold_s, early: bool = False):
             try:
-                await asyncio.sleep(hold_s)
+                await asyncio.sleep(delay)
             except asyncio.CancelledError:
                 return
             combined = st["pending"].strip()
             st["pending"] = ""
             st["debounce"] = None
+            rec = st["turn"]
+            if rec is not None and not rec["done"]:
+                rec["task"].cancel()  # an answer after the commit changes nothing: counted unknown
+            if early:
+                m.inc("turn_early_commits")
             if combined:
                 await process(combined)
 
-        def start_debounce():
-            t = asyncio.ensure_future(debounced())
+        def start_debounce(delay: float = hold_s, early: bool = False):
+            t = asyncio.ensure_future(debounced(delay, early))
             st["debounce"] = t
             st["procs"].add(t)  # (tracked until done: a disconnect lets a committing call finish)
             t.add_done_callback(st["procs"].discard)
 
+        async def run_turn(rec):
+            """One /turn call (NOT under the per-connection brain lock: it changes no context) and
+            its verdict: complete, incomplete, or unknown for anything but a well-formed answer."""
+            t0 = time.perf_counter()
+            p_end = None
+            try:
+                async with app["http"].post(turn_url, json={"text": rec["text"], "context": st["context"]},
+                                            timeout=aiohttp.ClientTimeout(total=5)) as resp:
+                    status, body = resp.status, await resp.text()
+                if status == 501:
+                    if not turn_state["unsupported"]:
+                        turn_state["unsupported"] = True
+                        print(f"[voice] the brain at {turn_url} has no turn probe (501): VWA_TURN is ignored from "
+                              "here on", flush=True)
+                elif status == 200:
+                    p = json.loads(body).get("p_end")
+                    if isinstance(p, (int, float)) and not isinstance(p, bool) and 0.0 <= p <= 1.0:
+                        p_end = float(p)
+            except asyncio.CancelledError:
+                pass
+            except Exception:  # noqa: BLE001  (refused, timed out, not JSON, not an object)
+                pass
+            rec["done"] = True
+            if p_end is None:
+                m.inc("turn_unknown")
+                return
+            m.observe("turn_ms", (time.perf_counter() - t0) * 1e3)
+            rec["complete"] = p_end >= turn_threshold
+            m.inc("turn_complete" if rec["complete"] else "turn_incomplete")
+            if rec["complete"]:
+                commit_early(rec)
+
+        def ask_turn(cand: str):
+            """Ask the brain whether ``cand`` is a finished command, once per text."""
+            rec = st["turn"]
+            if not turn_on or turn_state["unsupported"] or st["closed"] or (rec is not None and rec["text"] == cand):
+                return
+            if rec is not None and not rec["done"]:
+                rec["task"].cancel()  # superseded: its text is no longer what is pending
+            m.inc("turn_probes")
+            rec = st["turn"] = {"text": cand, "done": False, "complete": False, "task": None}
+            rec["task"] = asyncio.ensure_future(run_turn(rec))
+
+        def commit_early(rec):
+            """Re-arm the commit of a command judged complete -- only if the verdict is the latest,
+            is for exactly the pending text, and the commit the final armed is still armed (not
+            cancelled by SpeechStarted, not fired)."""
+            if rec is not st["turn"] or not rec["complete"] or st["debounce"] is None or st["t_final"] is None \
+                    or st["pending"].strip() != rec["text"]:
+                return
+            st["debounce"].cancel()
+            start_debounce(max(0.0, st["t_final"] + early_s - time.perf_counter()), early=True)
+
         def on_speculative_final(text: str):
             """The ASR's speculative final pass finished (the user has been silent for
-            VWA_SPEC_FINAL_MS): parse pending + it now, commit later (process)."""
+            VWA_SPEC_FINAL_MS): parse pending + it now, commit later (process); with VWA_TURN, ask
+            whether pending + it is a finished command (independent of VWA_SPEC_BRAIN)."""
             text = (text or "").strip()
-            if not spec_brain or not text or st["closed"]:
+            if not text or st["closed"]:
                 return
             cand = f"{st['pending']} {text}" if st["pending"] else text
+            ask_turn(cand.strip())
+            if not spec_brain:
+                return
             sp = st["spec"]
             if sp is not None and sp["text"] == cand and sp["ctx"] == st["ctx"]:
                 return
@@ -430,6 +519,14 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
                     m.inc("longform_finals")
                     continue
                 start_debounce()
+                if turn_on:
+                    # the full hold is armed; a verdict for exactly this text shortens it, now or
+                    # when it arrives; without one (no speculative pass, or another text) ask now
+                    rec, pend = st["turn"], st["pending"].strip()
+                    if rec is not None and rec["text"] == pend:
+                        commit_early(rec)
+                    else:
+                        ask_turn(pend)
 
         app["live"] += 1
         try:
@@ -476,6 +573,8 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
             st["closed"] = True
             if st["debounce"] is not None:
                 st["debounce"].cancel()  # (still sleeping: a command nobody finished saying)
+            if st["turn"] is not None and not st["turn"]["done"]:
+                st["turn"]["task"].cancel()
             if asr is not None and hasattr(asr, "close"):
                 asr.close()
             # queued executions still run (the reference's fire-and-forget promises do); their
