@@ -19,7 +19,13 @@ grammar-constrained decoding:
   how likely the transcript is a finished command.  Its prompt is the ``/parse`` prompt cut inside
   the user turn's ``{"text":"...`` (prompt.turn_tail); it is prefilled behind the same cached prefix,
   its last prompt token joins one ragged step, and the probability that the next token closes the
-  string is read off its logits row by one ``ops.set_logprob`` launch -- nothing is decoded.
+  string is read off its logits row by one ``ops.set_logprob`` launch -- nothing is decoded;
+* **summaries** (``summary`` / ``summary_async`` / ``submit_summary``): a request of a third kind, free
+  text inside ``{"summary":"..."}``.  It has its own prompt head, its own grammar and its own sampling
+  parameters (temperature, top-p, top-k, repetition penalty over its own sampled tokens).  Its rows
+  are sampled rows after the parse rows; an iteration that holds one runs one ``ops.nucleus_step``
+  launch over all sampled rows in front of the sampler (parse rows pass through), an iteration
+  without one launches exactly what it did before.
 
 `FakeIntentEngine` is the test double (the reference mocks callLLMJSON with vi.spyOn,
 apps/brain/test/parse.test.ts:7-21).
@@ -38,8 +44,8 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..grammar import CompiledGrammar, intent_grammar
-from .prompt import llama3_chat, messages_for, turn_tail
+from ..grammar import CompiledGrammar, intent_grammar, summary_grammar
+from .prompt import llama3_chat, messages_for, summary_messages, turn_tail
 
 
 class IntentEngineError(RuntimeError):
@@ -69,8 +75,18 @@ class IntentRequest:
     future: Any = None
     diag: Optional[str] = None
     kind: str = "parse"                 # "turn": a turn-completion probe (no matcher, nothing sampled)
-    probe_text: Optional[str] = None
+    probe_text: Optional[str] = None    # "summary": free text under the summary grammar
     result: Optional[Dict[str, Any]] = None
+    head_len: int = 0                   # tokens of this request's static head: what _finish publishes
+    # summaries: the page, the sampling parameters (temperature, top_p, top_k, penalty), the ids of
+    # the answer tokens the sampler drew (not the forced ones) -- the repetition penalty's history
+    page: Optional[Dict[str, Any]] = None
+    max_chars: int = 0
+    sampling: Tuple[float, float, int, float] = (0.0, 1.0, 0, 1.0)
+    sampled: List[int] = field(default_factory=list)
+    page_tokens: int = 0
+    truncated: bool = False
+    n_kept: int = 0
 
     def stats(self, t_end: float) -> Dict[str, Any]:
         return dict(prompt_tokens=len(self.ids), cached_prefix_tokens=self.cached,
@@ -158,6 +174,22 @@ class LLMIntentEngine:
         self.keep_turn_trace = False
         self.last_turn_trace: List[Dict[str, Any]] = []
         self.last_turn_stats: Dict[str, Any] = {}
+        # summaries: per-row sampling parameters and history for ops.nucleus_step, staged in one pinned
+        # buffer ([temperature | top_p | top_k | penalty] x R, then R x H history ids) and copied in one
+        # piece; the narrowed masks and the kept counts it writes; the traced-run record (off by default)
+        H = self.summary_history = 64
+        self.summary_max_steps = 2048
+        self.summary_defaults = dict(max_chars=400, temperature=0.7, top_p=0.9, top_k=50, penalty=1.1)
+        self.h_nuc = torch.zeros(4 * R + R * H, dtype=torch.int32, pin_memory=pin)
+        self.d_nuc = torch.zeros(4 * R + R * H, dtype=torch.int32, device=dev)
+        self.h_nuc_np = self.h_nuc.numpy()
+        self.d_nuc_mask = torch.zeros(R, W, dtype=torch.int32, device=dev)
+        self.d_nkept = torch.zeros(R, dtype=torch.int32, device=dev)
+        self.keep_summary_trace = False
+        self._nuc_traced = 0
+        self.last_summary_trace: List[Dict[str, Any]] = []
+        self.last_summary_stats: Dict[str, Any] = {}
+        self.summary_stats = dict(summaries=0, summary_tokens=0, n_kept_sum=0, nucleus_launches=0)
         self.waiting: Deque[IntentRequest] = deque()
         self.active: List[IntentRequest] = []
         self._lock = threading.Lock()
@@ -173,8 +205,10 @@ class LLMIntentEngine:
         ids = self._prefix_ids.get(head)
         if ids is None:
             ids = self.tok.encode(head)
-            self._prefix_ids = {head: ids}
-        self._head_len = len(ids)
+            if len(self._prefix_ids) >= 4:  # the parse head and the summary head, with room for a changed one
+                self._prefix_ids.pop(next(iter(self._prefix_ids)))
+            self._prefix_ids[head] = ids
+        self._head_len = len(ids)  # of the prompt encoded last: a request keeps its own (head_len)
         return ids + self.tok.encode(tail)
 
     def grammar_bytes(self, tok: int) -> bytes:
@@ -210,12 +244,15 @@ class LLMIntentEngine:
         r.t_start = time.perf_counter()
         if r.kind == "turn":
             r.ids = self._encode_head_tail(*turn_tail(r.probe_text, self.chat_format))
+        elif r.kind == "summary":
+            self._encode_summary(r)
         else:
             r.ids = self._encode_prompt(r.messages)
             r.matcher = self.grammar.matcher(self.budget_chars)
             if r.matcher.min_completion() > self.budget_chars:
                 raise IntentEngineError(f"budget_chars={self.budget_chars} is below the shortest schema-valid "
                                         f"answer ({r.matcher.min_completion()} chars)")
+        r.head_len = self._head_len
         r.seq = eng.new_sequence(r.ids)
         r.cached = r.seq.n_computed
         if r.cached >= len(r.ids):  # whole prompt cached: recompute its last token for logits
@@ -235,18 +272,28 @@ class LLMIntentEngine:
         if r.seq is not None:
             # only the static system + few-shot prefix is shared across requests; the request's
             # own suffix and answer are never served from cache (no replay of repeated commands)
-            self.engine.free_sequence(r.seq, publish_upto=self._head_len)
+            self.engine.free_sequence(r.seq, publish_upto=r.head_len)
             r.seq = None
         r.t_end = time.perf_counter()
         if r.kind == "turn":
             if r.result is not None:
                 r.result["ms"] = (r.t_end - r.t_submit) * 1e3
                 self.last_turn_stats = r.result
+        elif r.kind == "summary":
+            if error is None:
+                text = json.loads(r.text)["summary"]
+                r.result = dict(summary=text, chars=len(text), prompt_tokens=len(r.ids),
+                                cached_prefix_tokens=r.cached, page_tokens=r.page_tokens, truncated=r.truncated,
+                                decode_steps=r.steps, ms=(r.t_end - r.t_submit) * 1e3)
+                self.last_summary_stats = dict(r.result, **r.stats(r.t_end))
+                self.summary_stats["summaries"] += 1
+                self.summary_stats["summary_tokens"] += r.steps
+                self.summary_stats["n_kept_sum"] += r.n_kept
         else:
             self.last_stats = r.stats(r.t_end)
         if r.future is not None:
             if error is None:
-                r.future.set_result(r.result if r.kind == "turn" else r.text)
+                r.future.set_result(r.result if r.kind in ("turn", "summary") else r.text)
             else:
                 r.future.set_exception(error)
 
@@ -302,9 +349,11 @@ class LLMIntentEngine:
         # given to the sampler: the sampled requests' row indices, their mask rows and the
         # sampler's step counter are what they would be without the probes
         probes: List[IntentRequest] = []
+        # summaries are sampled rows after the parse rows: the parse rows keep their row indices, mask
+        # rows and (with the one sampler launch per iteration) the sampler's step counter
         order = self.active
-        if any(r.kind == "turn" for r in order):
-            order = [r for r in order if r.kind != "turn"] + [r for r in order if r.kind == "turn"]
+        if any(r.kind != "parse" for r in order):
+            order = [r for k in ("parse", "summary", "turn") for r in order if r.kind == k]
         for r in order:
             if not r.feed or budget <= 0:
                 continue
@@ -353,7 +402,13 @@ class LLMIntentEngine:
         logits = self.engine.head_logits(col_mask=mask if self.masked_head else None, mask_rows=n + p, gather=False)
         if p:
             self._probe_launch(logits, n, p)  # (before the sampler, on the same stream)
-        if n:
+        ns = sum(r.kind == "summary" for r in batch)
+        if ns:
+            # one nucleus launch over all sampled rows, in front of the sampler (parse rows pass
+            # through): the sampler then reads the narrowed device masks and per-row temperatures
+            self._nucleus_launch(logits, batch, n, mask)
+            toks = self._sample(logits[:n], n, self.engine.step_fail_word(), narrowed=True)
+        elif n:
             toks = self._sample(logits[:n], n, self.engine.step_fail_word())
         else:  # probes only: no sampler launch, the sampler's step counter does not move
             toks = []
@@ -363,7 +418,11 @@ class LLMIntentEngine:
             # sampler's fail word): re-run the step on the per-kernel path and sample again
             self.engine.host_synced()
             logits = self.engine.recover_step()
-            toks = self._sample(logits[:n], n, None)
+            if ns:
+                # the re-run logits are fresh (unpenalised): the step runs on them once more, penalty
+                # included -- the rows the failed launch penalised are not read again
+                self._nucleus_launch(logits, batch, n, mask, rerun=True)
+            toks = self._sample(logits[:n], n, None, narrowed=bool(ns))
             if p:
                 self._probe_launch(logits, n, p)  # the probes too, from the re-run logits
         if p:
@@ -374,6 +433,8 @@ class LLMIntentEngine:
         tm["sample_launch_ms"] += (self._t3 - t2) * 1e3
         tm["gpu_wait_ms"] += (t4 - self._t3) * 1e3
         self.batch_stats["sampled"] += n
+        if ns:
+            self._nucleus_finish(batch, toks, n)
         if any(t == -1 for t in toks):
             self._diagnose(batch, toks, logits, n)
         self._accept(batch, toks, finished)
@@ -382,13 +443,19 @@ class LLMIntentEngine:
         tm["post_ms"] += (time.perf_counter() - t4) * 1e3
         return finished
 
-    def _sample(self, logits: torch.Tensor, n: int, fail_word: Optional[torch.Tensor]) -> List[int]:
-        """Masked sampling of the n logits rows (masks already in d_mask) and the token readback."""
+    def _sample(self, logits: torch.Tensor, n: int, fail_word: Optional[torch.Tensor],
+                narrowed: bool = False) -> List[int]:
+        """Masked sampling of the n logits rows (masks already in d_mask) and the token readback.
+        ``narrowed``: an iteration with summary rows -- the masks are the nucleus step's output and the
+        temperatures the per-row ones it was given."""
         zc = self.zero_copy
         if zc and self.spin_wait:
             self.h_tok_np[:n] = _TOK_PENDING  # before the launch: the sampler stores into it directly
-        self.engine.sample(logits, mask=self.h_mask if zc else self.d_mask,
-                           temperature=self.d_temp if self.temperature > 0 else None, seed=self.d_seed,
+        if narrowed:
+            mask, temperature = self.d_nuc_mask, self._nuc_views()[0]
+        else:
+            mask, temperature = self.h_mask if zc else self.d_mask, self.d_temp if self.temperature > 0 else None
+        self.engine.sample(logits, mask=mask, temperature=temperature, seed=self.d_seed,
                            step=self.d_step, out_tokens=self.h_tok if zc else self.d_tok,
                            part_val=self.part_val[: n * 64], part_idx=self.part_idx[: n * 64], fail_word=fail_word)
         if self.dev.type == "cuda" and zc and self.spin_wait:
@@ -435,6 +502,140 @@ class LLMIntentEngine:
             toks = self.d_tok[:n].tolist()
         self._t3 = t3
         return toks
+
+    # ------------------------------------------------------------------ summaries
+    def _nuc_views(self, host: bool = False):
+        """(temperature f32, top_p f32, top_k i32, penalty f32, history i32 [R, H]) views of the staged
+        parameter buffer, on the device (or the host copy)."""
+        R, H = self.max_active, self.summary_history
+        b = self.h_nuc if host else self.d_nuc
+        return (b[:R].view(torch.float32), b[R : 2 * R].view(torch.float32), b[2 * R : 3 * R],
+                b[3 * R : 4 * R].view(torch.float32), b[4 * R :].view(R, H))
+
+    def _encode_summary(self, r: IntentRequest) -> None:
+        """The summary prompt, the page text cut by tokens so that prompt + worst-case answer (every
+        byte of the matcher's budget a token) fits max_model_len; the request's matcher."""
+        g = summary_grammar(self.tok, r.max_chars)
+        if g.words != self.grammar.words:
+            raise IntentEngineError("the summary grammar's mask width differs from the intent grammar's")
+        budget = 4 * r.max_chars + 16  # bytes: UTF-8 at its widest, the JSON around the string
+        r.matcher = g.matcher(budget)
+        room = self.engine.max_model_len - budget - 2
+        page = r.page
+        text = page["text"].strip()
+        ids = self._encode_head_tail(*self.chat_format(summary_messages(text, page.get("title"), page.get("url"))))
+        page_ids = self.tok.encode(text)
+        keep = len(page_ids)
+        while len(ids) > room:
+            keep = min(keep - 1, keep - (len(ids) - room))
+            if keep < 1:
+                raise IntentEngineError(f"max_chars={r.max_chars} leaves no room for the page within "
+                                        f"max_model_len={self.engine.max_model_len}")
+            r.truncated = True
+            text = self.tok.decode(page_ids[:keep]).strip()
+            ids = self._encode_head_tail(*self.chat_format(summary_messages(text, page.get("title"), page.get("url"))))
+        r.page_tokens = len(self.tok.encode(text)) if r.truncated else len(page_ids)
+        r.ids = ids
+
+    def _nucleus_launch(self, logits: torch.Tensor, batch: List[IntentRequest], n: int, mask: torch.Tensor,
+                        rerun: bool = False) -> None:
+        """One ops.nucleus_step launch over the n sampled rows (64 per launch at most): parse rows get
+        pass-through parameters (top_k 0, top_p 1, penalty 1), summary rows their own and the ids they
+        sampled last.  The narrowed masks land in d_nuc_mask, the kept counts in d_nkept."""
+        R, H = self.max_active, self.summary_history
+        hv = self.h_nuc_np
+        fv = hv.view(np.float32)
+        hist = hv[4 * R :].reshape(R, H)
+        for i, r in enumerate(batch):
+            if r.kind == "summary":
+                T, p, k, th = r.sampling
+                h = r.sampled[-H:]
+            else:
+                T, p, k, th, h = max(float(self.temperature), 0.0), 1.0, 0, 1.0, ()
+            fv[i], fv[R + i], hv[2 * R + i], fv[3 * R + i] = T, p, k, th
+            hist[i, : len(h)] = h
+            hist[i, len(h) :] = -1
+        self.d_nuc.copy_(self.h_nuc, non_blocking=True)
+        dT, dp, dk, dth, dh = self._nuc_views()
+        trace = self.keep_summary_trace
+        pre = logits[:n].clone() if trace else None
+        V = logits.shape[1]
+        for i in range(0, n, ops.NUCLEUS_MAX_ROWS):
+            j = min(n, i + ops.NUCLEUS_MAX_ROWS)
+            ops.nucleus_step(logits[i:j], mask[i:j], self.d_nuc_mask[i:j], self.d_nkept[i:j], dT[i:j], dp[i:j],
+                             dk[i:j], dth[i:j], dh[i:j], vocab=V)
+            self.summary_stats["nucleus_launches"] += 1
+        if trace:
+            if rerun and self._nuc_traced:  # the failed launch's records describe logits nobody sampled from
+                del self.last_summary_trace[-self._nuc_traced :]
+            self._nuc_traced = 0
+            hT, hp, hk, hth, hh = self._nuc_views(host=True)
+            for i, r in enumerate(batch):
+                if r.kind == "summary":
+                    self.last_summary_trace.append(dict(
+                        request=r, row=i, step=r.steps, rows=n, logits=pre[i].detach().cpu(),
+                        mask_in=mask[i].detach().cpu().clone(), temperature=float(hT[i]), top_p=float(hp[i]),
+                        top_k=int(hk[i]), penalty=float(hth[i]), history=hh[i].clone()))
+                    self._nuc_traced += 1
+
+    def _nucleus_finish(self, batch: List[IntentRequest], toks: List[int], n: int) -> None:
+        """After the tokens are back: the summary rows' kept counts (read after a stream synchronise, as
+        the probes' results are) into the requests' statistics, and the traced rows' outputs."""
+        if self.dev.type == "cuda":
+            torch.cuda.current_stream().synchronize()
+        kept = self.d_nkept[:n].tolist()
+        for i, r in enumerate(batch):
+            if r.kind == "summary":
+                r.n_kept += kept[i]
+        if self.keep_summary_trace:
+            out = self.d_nuc_mask[:n].cpu()
+            for tr in self.last_summary_trace[-self._nuc_traced :]:
+                i = tr["row"]
+                tr.update(mask_out=out[i].clone(), n_kept=kept[i], token=toks[i])
+
+    def submit_summary(self, text: str, title: Optional[str] = None, url: Optional[str] = None, *,
+                       max_chars: Optional[int] = None, temperature: Optional[float] = None,
+                       top_p: Optional[float] = None, top_k: Optional[int] = None, penalty: Optional[float] = None,
+                       future=None) -> IntentRequest:
+        """Queue a summary of the page ``text`` (admitted like any request)."""
+        if getattr(getattr(self.engine.model, "tp", None), "size", 1) > 1:
+            raise IntentEngineError("summaries are not supported under tensor parallelism (vocab-parallel logits)")
+        if not isinstance(text, str) or not text.strip():
+            raise IntentEngineError("summary: text must be a non-empty string")
+        d = self.summary_defaults
+        pick = lambda v, k: d[k] if v is None else v  # noqa: E731
+        max_chars = int(pick(max_chars, "max_chars"))
+        T, p, k, th = (float(pick(temperature, "temperature")), float(pick(top_p, "top_p")), int(pick(top_k, "top_k")),
+                       float(pick(penalty, "penalty")))
+        if not 1 <= max_chars <= 4096:
+            raise IntentEngineError("summary: max_chars must be in [1, 4096]")
+        if not 0 <= k <= ops.NUCLEUS_MAX_TOP_K or (p < 1.0 and k < 1) or not p > 0.0 or not th > 0.0:
+            raise IntentEngineError("summary: top_k must be in [0, 1024] (>= 1 with top_p < 1), top_p and penalty > 0")
+        r = IntentRequest(messages=[], t_submit=time.perf_counter(), future=future, kind="summary",
+                          page=dict(text=text, title=title, url=url), max_chars=max_chars, sampling=(T, p, k, th))
+        with self._lock:
+            self.waiting.append(r)
+            self._wake.notify()
+        return r
+
+    def summary_async(self, text: str, title: Optional[str] = None, url: Optional[str] = None, **kw):
+        """concurrent.futures.Future resolved with the summary's dict (requires start())."""
+        fut: Future = Future()
+        self.submit_summary(text, title, url, future=fut, **kw)
+        return fut
+
+    def summary(self, text: str, title: Optional[str] = None, url: Optional[str] = None, **kw) -> Dict[str, Any]:
+        """A spoken-style summary of a page: ``{"summary", "chars", "prompt_tokens", "cached_prefix_tokens",
+        "page_tokens", "truncated", "decode_steps", "ms"}``.  Through the background scheduler when it
+        runs, otherwise by stepping here."""
+        if self._thread is not None:
+            return self.summary_async(text, title, url, **kw).result()
+        r = self.submit_summary(text, title, url, **kw)
+        while not r.done:
+            self.step()
+        if r.error is not None:
+            raise r.error
+        return r.result
 
     # ------------------------------------------------------------------ turn probes
     def end_set_ids(self) -> List[int]:
@@ -542,10 +743,12 @@ class LLMIntentEngine:
                                                   + (f": {r.diag}" if getattr(r, "diag", None) else "")))
             else:
                 r.out += self.grammar_bytes(tok)
+                if r.kind == "summary":
+                    r.sampled.append(tok)
                 if m.is_accept():
                     r.seq.tokens.append(tok)
                     self._finish(r)
-                elif r.steps >= self.max_steps:
+                elif r.steps >= (self.summary_max_steps if r.kind == "summary" else self.max_steps):
                     self._finish(r, IntentEngineError("decode step limit reached"))
                 else:
                     r.feed = [tok]

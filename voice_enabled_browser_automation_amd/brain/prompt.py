@@ -167,3 +167,22 @@ def turn_tail(text: str, chat_format=llama3_chat) -> Tuple[str, str]:
     opening = '{"text":' + json.dumps(t, ensure_ascii=False)[:-1]
     at = tail.index(opening)  # (the user turn's content starts with it: compact() writes "text" first)
     return head, tail[: at + len(opening)]
+
+
+SUMMARY_PROMPT = (
+    "You summarise a web page for someone who is listening, not reading. Reply with JSON only: "
+    "{\"summary\": \"...\"}. The summary is two or three short spoken sentences in plain language that say "
+    "what the page is and what matters most on it. No lists, no markup, no urls, nothing that is not on the page."
+)
+
+
+def summary_messages(text: str, title: str = None, url: str = None) -> List[Dict[str, str]]:
+    """Chat messages (system, user) of a page summary.  The static head is the system turn alone --
+    distinct from the parse head, so the two are cached side by side -- and the user message holds the
+    page's title, url and visible text, the text last so that a cut of it cuts nothing else.  ``<|`` is
+    broken up: page text must not spell a chat token."""
+    def clean(s) -> str:
+        return (s or "").replace("<|", "< |").strip()
+
+    return [{"role": "system", "content": SUMMARY_PROMPT},
+            {"role": "user", "content": f"Title: {clean(title)}\nURL: {clean(url)}\nPage text:\n{clean(text)}"}]

@@ -1,5 +1,6 @@
 """Brain service: ``GET /health``, ``POST /parse``, ``GET /metrics`` (parity with apps/brain/src/server.ts),
-and ``POST /turn``, this project's own: the turn-completion probe.
+and ``POST /turn`` and ``POST /summarize``, this project's own: the turn-completion probe and the page
+summary behind the ``summarize`` intent.
 
 Request flow (apps/brain/src/server.ts:89-139):
   ParseRequest validation -> 400 {error:"invalid_request", detail}
@@ -12,6 +13,13 @@ Request flow (apps/brain/src/server.ts:89-139):
 ``POST /turn`` {"text", "context"?}: 400 invalid_request for a missing, empty or non-string text;
 501 {error:"turn_unsupported"} for an engine without ``turn_async`` (keyword, TP); 500 llm_error as
 ``/parse``; 200 {p_end, logprob, prompt_tokens, cached_prefix_tokens, ms}.
+
+``POST /summarize`` {"text", "title"?, "url"?, "max_chars"?}: 400 invalid_request for a missing, empty
+or non-string text, a non-string title or url, or a max_chars that is not an integer in [16, 4096];
+501 {error:"summarize_unsupported"} for an engine without ``summary_async`` (keyword, TP); 500 llm_error
+as ``/parse``; 200 {summary, chars, prompt_tokens, cached_prefix_tokens, page_tokens, truncated,
+decode_steps, ms}.  ``/metrics`` counts ``summaries`` and ``summary_tokens`` and gives the mean ``n_kept``
+(ids the nucleus step left per sampled token).
 
 With the LLM engine the grammar makes the first answer schema-valid, so the repair path only
 runs for engines without constrained decoding (or injected faults in tests).
@@ -35,6 +43,8 @@ from ..utils.metrics import Metrics
 from .prompt import messages_for
 from .tp_engine import TPIntentEngine  # noqa: F401  (re-exported: the TP control plane)
 from ..utils.env import knob
+
+SUMMARY_MIN_CHARS, SUMMARY_MAX_CHARS = 16, 4096  # a request's max_chars
 
 SERVICE_NAME = "brain-ts"  # byte-compatible /health payload (apps/brain/src/server.ts:87)
 
@@ -61,6 +71,11 @@ def build_app(engine: Any = None) -> web.Application:
             snap["last_request"] = st
         if hasattr(eng, "engine_stats"):
             snap["engine"] = eng.engine_stats()
+        ss = getattr(eng, "summary_stats", None)
+        if ss is not None:
+            snap["summaries"] = ss["summaries"]
+            snap["summary_tokens"] = ss["summary_tokens"]
+            snap["summary_mean_n_kept"] = round(ss["n_kept_sum"] / ss["summary_tokens"], 3) if ss["summary_tokens"] else 0.0
         return web.json_response(snap)
 
     async def call(eng, messages):
@@ -151,11 +166,49 @@ def build_app(engine: Any = None) -> web.Application:
         m.inc("turn_ok")
         return web.json_response(out)
 
+    async def summarize(req: web.Request) -> web.Response:
+        """A spoken-style summary of a page's text (LLMIntentEngine.summary): what the executor's
+        summarize intent asks for."""
+        m: Metrics = app["metrics"]
+        t0 = time.perf_counter()
+        try:
+            body = await req.json()
+        except Exception:  # noqa: BLE001
+            body = None
+        body = body if isinstance(body, dict) else {}
+        text, max_chars = body.get("text"), body.get("max_chars")
+        ok = isinstance(text, str) and bool(text.strip()) \
+            and all(body.get(k) is None or isinstance(body.get(k), str) for k in ("title", "url")) \
+            and (max_chars is None or (isinstance(max_chars, int) and not isinstance(max_chars, bool)
+                                       and SUMMARY_MIN_CHARS <= max_chars <= SUMMARY_MAX_CHARS))
+        if not ok:
+            m.inc("invalid_request")
+            return web.json_response({"error": "invalid_request",
+                                      "detail": "body must be {\"text\": non-empty string, \"title\"?: string, "
+                                                f"\"url\"?: string, \"max_chars\"?: integer in [{SUMMARY_MIN_CHARS}, "
+                                                f"{SUMMARY_MAX_CHARS}]}}"}, status=400)
+        eng = app["engine"]
+        if not hasattr(eng, "summary_async"):
+            m.inc("summarize_unsupported")
+            return web.json_response({"error": "summarize_unsupported"}, status=501)
+        try:
+            if hasattr(eng, "start"):
+                eng.start()
+            kw = {} if max_chars is None else {"max_chars": max_chars}
+            out = dict(await asyncio.wrap_future(eng.summary_async(text, body.get("title"), body.get("url"), **kw)))
+        except Exception as e:  # noqa: BLE001
+            m.inc("llm_error")
+            return web.json_response({"error": "llm_error", "detail": str(e) or e.__class__.__name__}, status=500)
+        m.observe("summarize_ms", (time.perf_counter() - t0) * 1e3)
+        m.inc("summarize_ok")
+        return web.json_response(out)
+
     app.on_cleanup.append(on_cleanup)
     app.router.add_get("/health", health)
     app.router.add_get("/metrics", metrics)
     app.router.add_post("/parse", parse)
     app.router.add_post("/turn", turn)
+    app.router.add_post("/summarize", summarize)
     return app
 
 
@@ -168,6 +221,16 @@ def make_engine_from_env():
     if kind == "llm":
         return build_llm_engine()
     raise ValueError(f"unknown VWA_BRAIN_ENGINE={kind!r}")
+
+
+def summary_defaults_from_env(ie):
+    """The summary defaults of an LLMIntentEngine from the summary knobs (VWA_SUMMARY_MAX_CHARS, _TEMPERATURE, _TOP_P, _TOP_K, _PENALTY); the default length is
+    lowered where it would take more than half of the model's window (GPT-2's 1024 tokens)."""
+    fit = max(SUMMARY_MIN_CHARS, (ie.engine.max_model_len // 2 - 16) // 4)
+    ie.summary_defaults = dict(max_chars=min(knob("VWA_SUMMARY_MAX_CHARS"), fit),
+                               temperature=knob("VWA_SUMMARY_TEMPERATURE"), top_p=knob("VWA_SUMMARY_TOP_P"),
+                               top_k=knob("VWA_SUMMARY_TOP_K"), penalty=knob("VWA_SUMMARY_PENALTY"))
+    return ie
 
 
 def build_llm_engine(model_name: Optional[str] = None, device: Optional[str] = None):
@@ -197,7 +260,8 @@ def build_llm_engine(model_name: Optional[str] = None, device: Optional[str] = N
         model = load_llm(name, device=dev, seed=seed, weights_path=wpath)
         eng = LLMEngine(model, max_seqs=sessions, max_model_len=cfg.max_pos)
         eng.capture_all()
-        return LLMIntentEngine(eng, load_tokenizer("gpt2"), budget_chars=budget, chat_format=plain_chat)
+        return summary_defaults_from_env(
+            LLMIntentEngine(eng, load_tokenizer("gpt2"), budget_chars=budget, chat_format=plain_chat))
     tp = init_distributed(tp_size=knob("VWA_TP"))
     model = load_llm(name, device=dev, tp=tp, seed=seed, weights_path=wpath,
                      wdtype=knob("VWA_DTYPE"))
@@ -209,7 +273,8 @@ def build_llm_engine(model_name: Optional[str] = None, device: Optional[str] = N
         hold = knob("VWA_ASR_BUSY_HOLD_MS")
         eng.chain_gate = lambda: flag.busy(hold)
     eng.capture_all()
-    ie = LLMIntentEngine(eng, load_tokenizer("llama3"), budget_chars=budget, chat_format=llama3_chat)
+    ie = summary_defaults_from_env(
+        LLMIntentEngine(eng, load_tokenizer("llama3"), budget_chars=budget, chat_format=llama3_chat))
     return TPIntentEngine(ie, tp) if tp.size > 1 else ie
 
 

@@ -35,6 +35,22 @@ LEGACY_SEARCH_SELECTORS = ['input[name="q"]', 'input[type="search"]', 'input[ari
                            'input[placeholder*="Search" i]', "#search", 'input[name*="search" i]']
 UPLOAD_DIR = knob("UPLOAD_DIR")
 
+# what the summarize intent reads off the page (one evaluate: Playwright and the CDP driver alike)
+PAGE_TEXT_JS = ("() => ({title: document.title || '', url: location.href || '', "
+                "text: document.body ? document.body.innerText : ''})")
+
+
+def summarize_url() -> str:
+    """VWA_SUMMARIZE_URL, or BRAIN_URL with /parse replaced by /summarize (as the voice service derives
+    its /turn URL)."""
+    url = knob("VWA_SUMMARIZE_URL")
+    if url:
+        return url
+    brain = knob("BRAIN_URL")
+    base, sep, rest = brain.rpartition("/parse")
+    return base + "/summarize" + rest if sep else brain.rstrip("/") + "/summarize"
+
+
 EXTRACT_JS = r"""
 ([sel, limit, columns]) => {
   let cards = [];
@@ -327,7 +343,38 @@ class IntentRunner:
         step["screenshot"] = await self.cap((it.get("args") or {}).get("label") or "screenshot")
 
     async def do_summarize(self, it, step):
-        step["data"] = {"note": "summarize should be handled by the brain"}
+        """The reference leaves this to "the brain" and answers a note (apps/executor/src/actions.js:
+        244-248).  With VWA_SUMMARIZE the brain is asked: the page's title, url and visible text (capped
+        at VWA_SUMMARY_PAGE_CHARS) go to its POST /summarize and the summary becomes the step's data.
+        A brain error -- a 501 from an engine without summaries included -- fails the step with the
+        error's text, so ``retries`` applies."""
+        if not knob("VWA_SUMMARIZE"):
+            step["data"] = {"note": "summarize should be handled by the brain"}
+            return
+        import aiohttp
+
+        page = await self.page.evaluate(PAGE_TEXT_JS)
+        page = page if isinstance(page, dict) else {}
+        text = str(page.get("text") or "").strip()
+        source_chars = len(text)
+        if not text:
+            raise ValueError("summarize: the page has no visible text")
+        body = {"text": text[: knob("VWA_SUMMARY_PAGE_CHARS")], "title": str(page.get("title") or ""),
+                "url": str(page.get("url") or "")}
+        max_chars = (it.get("args") or {}).get("max_chars")
+        if isinstance(max_chars, int) and not isinstance(max_chars, bool):
+            body["max_chars"] = max_chars
+        async with aiohttp.ClientSession(timeout=aiohttp.ClientTimeout(total=_tmo(it) / 1e3 + 60)) as s:
+            async with s.post(summarize_url(), json=body) as resp:
+                try:
+                    out = await resp.json(content_type=None)
+                except Exception:  # noqa: BLE001
+                    out = None
+                if resp.status != 200 or not isinstance(out, dict) or not isinstance(out.get("summary"), str):
+                    detail = out.get("detail") or out.get("error") if isinstance(out, dict) else None
+                    raise RuntimeError(f"summarize: the brain answered {resp.status}" + (f": {detail}" if detail else ""))
+        step["data"] = {"summary": out["summary"], "chars": len(out["summary"]), "truncated": bool(out.get("truncated")),
+                        "source_chars": source_chars}
 
     HANDLERS = {
         "navigate": do_navigate, "search": do_search, "click": do_click, "filter": do_filter, "sort": do_sort,

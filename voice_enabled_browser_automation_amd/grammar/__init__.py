@@ -151,3 +151,30 @@ def intent_grammar(tokenizer, eos_ids: Optional[List[int]] = None, **kw) -> Comp
         eos_ids = [i for i in (tokenizer.token_to_id("<|eot_id|>"), tokenizer.token_to_id("<|end_of_text|>"),
                                tokenizer.token_to_id("<|endoftext|>")) if i is not None]
     return CompiledGrammar(ir, tokenizer.token_bytes(), eos_ids)
+
+
+def summary_schema(max_chars: int) -> Dict[str, Any]:
+    """Generation schema of a page summary: exactly one key, a string of at most ``max_chars`` characters."""
+    return {"type": "object", "properties": {"summary": {"type": "string", "maxLength": int(max_chars)}},
+            "required": ["summary"]}
+
+
+_SUMMARY_GRAMMARS: Dict[Any, CompiledGrammar] = {}
+
+
+def summary_grammar(tokenizer, max_chars: int, eos_ids: Optional[List[int]] = None) -> CompiledGrammar:
+    """``{"summary": <string, maxLength max_chars>}`` compiled for the tokenizer: the answer is valid JSON
+    by construction and jump-forward supplies ``{"summary":"``.  Compiled on first use and cached per
+    (tokenizer, max_chars); the mask width is the intent grammar's (same vocabulary)."""
+    key = (id(tokenizer), int(max_chars))
+    g = _SUMMARY_GRAMMARS.get(key)
+    if g is None:
+        if eos_ids is None:
+            eos_ids = [i for i in (tokenizer.token_to_id("<|eot_id|>"), tokenizer.token_to_id("<|end_of_text|>"),
+                                   tokenizer.token_to_id("<|endoftext|>")) if i is not None]
+        g = CompiledGrammar(ir_from_json_schema(summary_schema(max_chars)), tokenizer.token_bytes(), eos_ids)
+        g._tokenizer = tokenizer  # keeps id(tokenizer) from being reused while the entry lives
+        if len(_SUMMARY_GRAMMARS) >= 8:
+            _SUMMARY_GRAMMARS.pop(next(iter(_SUMMARY_GRAMMARS)))
+        _SUMMARY_GRAMMARS[key] = g
+    return g

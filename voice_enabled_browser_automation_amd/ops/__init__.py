@@ -1843,3 +1843,90 @@ def set_logprob(logits: torch.Tensor, vocab: int, sets: torch.Tensor, *,
     # (a missing library raises: there is no other GPU path)
     turn_ext().set_logprob(logits, vocab, sets, out)
     return out
+
+
+# ----------------------------------------------------------------------------- nucleus step
+NUCLEUS_MAX_ROWS = 64          # csrc/nucleus/nucleus.h kNucleusMaxRows: rows per launch
+NUCLEUS_MAX_VOCAB = 128256     # ... kNucleusMaxVocab (the Llama-3 vocabulary)
+NUCLEUS_MAX_TOP_K = 1024       # ... kNucleusMaxTopK
+NUCLEUS_MAX_HISTORY = 256      # ... kNucleusMaxHistory
+nucleus_launches = 0           # GPU launches of nucleus_step so far (the tests count them)
+
+
+def nucleus_ext():
+    """The nucleus step library ``_vwa_nucleus.so`` (loaded once). Raises if unavailable."""
+    return _load_lib("_vwa_nucleus", "nucleus step")
+
+
+def nucleus_step(logits: torch.Tensor, mask_in: Optional[torch.Tensor], mask_out: torch.Tensor, n_kept: torch.Tensor,
+                 temperature: torch.Tensor, top_p: torch.Tensor, top_k: torch.Tensor, penalty: torch.Tensor,
+                 history: torch.Tensor, *, vocab: Optional[int] = None) -> torch.Tensor:
+    """Repetition penalty, top-k and nucleus narrowing of the sampler's allow-mask, per row of f32
+    ``logits`` [rows <= 64, >= vocab] (csrc/nucleus/nucleus.h has the per-row rule).  The penalty is
+    applied to ``logits`` IN PLACE (once per distinct valid id of ``history`` int32 [>= rows, H <= 256]);
+    ``mask_out`` int32 [>= rows, >= ceil(vocab / 32)] gets ``mask_in`` (packed allow-bits, [1 or >= rows,
+    >= ceil(vocab / 32)], a GPU or pinned host tensor, or None: all allowed) narrowed to the ids kept,
+    ``n_kept`` int32 [>= rows] their count.  ``temperature``, ``top_p``, ``penalty`` (f32) and ``top_k``
+    (int32) are per row, [>= rows].  A row with top_k == 0 and top_p >= 1, or temperature <= 0, passes
+    its mask through.  One launch on the GPU, no host synchronisation; host tensors take the Python
+    reference and never load the library.  Returns ``mask_out``."""
+    global nucleus_launches
+    i32, f32, dev = torch.int32, torch.float32, logits.device
+    if logits.dim() != 2 or logits.dtype != f32 or logits.stride(1) != 1 \
+            or not (logits.shape[0] == 1 or logits.stride(0) >= logits.shape[1]) \
+            or not 1 <= logits.shape[0] <= NUCLEUS_MAX_ROWS or logits.shape[1] < 1:
+        raise ValueError(f"nucleus_step: logits must be float32 [1..{NUCLEUS_MAX_ROWS}, >= vocab] with contiguous rows "
+                         f"that do not overlap, not {logits.dtype} {tuple(logits.shape)}")
+    rows = logits.shape[0]
+    vocab = logits.shape[1] if vocab is None else int(vocab)
+    if not 1 <= vocab <= min(logits.shape[1], NUCLEUS_MAX_VOCAB):
+        raise ValueError(f"nucleus_step: vocab = {vocab} outside [1, {min(logits.shape[1], NUCLEUS_MAX_VOCAB)}] (the "
+                         "logits' row length, the library's limit)")
+    words = (vocab + 31) // 32
+    n1 = rows - 1
+    ins = [("logits", logits, 4 * (n1 * logits.stride(0) + vocab))]
+    if mask_in is not None:
+        m = mask_in
+        if m.dim() != 2 or m.dtype != i32 or m.stride(1) != 1 or m.shape[1] < words \
+                or not (m.shape[0] == 1 or (m.shape[0] >= rows and m.stride(0) >= m.shape[1])):
+            raise ValueError(f"nucleus_step: mask_in must be int32 [1 or >= {rows}, >= {words}] with contiguous rows "
+                             f"that do not overlap, not {m.dtype} {tuple(m.shape)}")
+        if m.device != dev and not (_gpu(logits) and m.device.type == "cpu" and m.is_pinned()):
+            raise ValueError(f"nucleus_step: mask_in is on {m.device} (and not pinned), the logits on {dev}")
+        ins.append(("mask_in", m, 4 * (n1 * (m.stride(0) if m.shape[0] > 1 else 0) + words)))
+    o = mask_out
+    if o.dim() != 2 or o.dtype != i32 or o.stride(1) != 1 or o.shape[0] < rows or o.shape[1] < words \
+            or not (o.shape[0] == 1 or o.stride(0) >= o.shape[1]):
+        raise ValueError(f"nucleus_step: mask_out must be int32 [>= {rows}, >= {words}] with contiguous rows that do "
+                         f"not overlap, not {o.dtype} {tuple(o.shape)}")
+    for name, t, dt in (("n_kept", n_kept, i32), ("temperature", temperature, f32), ("top_p", top_p, f32),
+                        ("top_k", top_k, i32), ("penalty", penalty, f32)):
+        if t.dim() != 1 or t.dtype != dt or not t.is_contiguous() or t.numel() < rows:
+            raise ValueError(f"nucleus_step: {name} must be contiguous {dt} [>= {rows}], not {t.dtype} "
+                             f"{tuple(t.shape)}")
+        if name != "n_kept":
+            ins.append((name, t, 4 * rows))
+    h = history
+    if h.dim() != 2 or h.dtype != i32 or h.shape[0] < rows or h.shape[1] > NUCLEUS_MAX_HISTORY \
+            or (h.shape[1] > 0 and (h.stride(1) != 1 or not (h.shape[0] == 1 or h.stride(0) >= h.shape[1]))):
+        raise ValueError(f"nucleus_step: history must be int32 [>= {rows}, <= {NUCLEUS_MAX_HISTORY}] with contiguous "
+                         f"rows that do not overlap, not {h.dtype} {tuple(h.shape)}")
+    if h.shape[1] > 0:
+        ins.append(("history", h, 4 * (n1 * h.stride(0) + h.shape[1])))
+    for name, t in (("mask_out", mask_out), ("n_kept", n_kept), ("temperature", temperature), ("top_p", top_p),
+                    ("top_k", top_k), ("penalty", penalty), ("history", history)):
+        if t.device != dev:
+            raise ValueError(f"nucleus_step: {name} is on {t.device}, the logits on {dev}")
+    outs = (("mask_out", mask_out, 4 * (n1 * mask_out.stride(0) + mask_out.shape[1])), ("n_kept", n_kept, 4 * rows))
+    for on, ot, ob in outs:
+        a = ot.data_ptr()
+        for name, t, nb in ins + [x for x in outs if x[0] != on]:
+            b = t.data_ptr()
+            if a < b + nb and b < a + ob:
+                raise ValueError(f"nucleus_step: {on} must not overlap {name}")
+    if not _gpu(logits):
+        return ref.nucleus_step(logits, vocab, mask_in, mask_out, n_kept, temperature, top_p, top_k, penalty, history)
+    # (a missing library raises: there is no other GPU path)
+    nucleus_ext().nucleus_step(logits, vocab, mask_in, mask_out, n_kept, temperature, top_p, top_k, penalty, history)
+    nucleus_launches += 1
+    return mask_out

@@ -659,3 +659,63 @@ def set_logprob(logits, vocab, sets, out):
         out[r, 0] = min(float(torch.logsumexp(x[hit], 0)) - A, 0.0) if bool(hit.any()) else ninf
         out[r, 1] = A
     return out
+
+
+def _pack_bits32(on: torch.Tensor, words: int) -> torch.Tensor:
+    """bool [n <= 32 words] -> the sampler's packed allow-bits, int32 [words]."""
+    bits = torch.zeros(words * 32, dtype=torch.int64)
+    bits[:on.numel()] = on.long()
+    v = (bits.view(words, 32) << torch.arange(32)).sum(1)
+    return torch.where(v >= 1 << 31, v - (1 << 32), v).to(torch.int32)
+
+
+def nucleus_step(logits, vocab, mask_in, mask_out, n_kept, temperature, top_p, top_k, penalty, history):
+    """The nucleus step on host tensors, as csrc/nucleus/nucleus.h states it, in f32: the penalty once
+    per distinct valid id, (logit descending, id ascending) candidates, the cut of the renormalised
+    top-k, pass-through rows.  The weights' sum runs left to right here (the kernel's order is its
+    own): the two agree wherever no c_j / C lies within rounding of top_p."""
+    ninf = float("-inf")
+    words = (vocab + 31) // 32
+    ids = torch.arange(vocab)
+    for r in range(logits.shape[0]):
+        x = logits[r]
+        th = penalty[r]
+        if float(th) != 1.0:
+            seen = set()
+            for t in history[r].tolist():
+                if 0 <= t < vocab and t not in seen:
+                    seen.add(t)
+                    x[t] = x[t] / th if float(x[t]) > 0.0 else x[t] * th
+        if mask_in is None:
+            on = torch.ones(vocab, dtype=torch.bool)
+        else:
+            row = mask_in[r if mask_in.shape[0] > 1 else 0]
+            on = ((row[ids >> 5] >> (ids & 31)) & 1).bool()
+        T, p = float(temperature[r]), float(top_p[r])
+        k = min(max(int(top_k[r]), 0), 1024)
+        keep_all = not p < 1.0
+        mask_out[r].zero_()
+        if not T > 0.0 or (k == 0 and keep_all):
+            mask_out[r, :words] = _pack_bits32(on, words)
+            n_kept[r] = int(on.sum())
+            continue
+        if k == 0:
+            k = 1024
+        cand = ids[on & (x[:vocab] > ninf)]
+        k = min(k, cand.numel())
+        if k == 0:
+            n_kept[r] = 0
+            continue
+        order = torch.sort(x[cand], descending=True, stable=True).indices[:k]   # ties keep id order
+        K = cand[order]
+        l = x[K]
+        n = k
+        if not keep_all:
+            c = torch.cumsum(torch.exp((l - l[0]) / temperature[r]), 0)
+            hit = torch.nonzero(c >= top_p[r] * c[-1])
+            n = int(hit[0]) + 1 if hit.numel() else k
+        keep = torch.zeros(vocab, dtype=torch.bool)
+        keep[K[:n]] = True
+        mask_out[r, :words] = _pack_bits32(keep, words)
+        n_kept[r] = n
+    return mask_out

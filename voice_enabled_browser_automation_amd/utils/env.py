@@ -109,6 +109,14 @@ class Settings(BaseModel):
     VWA_TURN_URL: Optional[str] = Field(None, description="voice -> brain /turn URL (default: BRAIN_URL with /parse replaced by /turn)")
     VWA_TURN_THRESHOLD: float = Field(0.5, gt=0.0, le=1.0, description="voice: a pending text whose probe answers p_end >= this is a finished command. In (0, 1]; 1.0 never commits early. 0.5 is a policy default and is NOT tuned on real speech or real weights")
     VWA_COMMIT_MIN_MS: float = Field(0.0, ge=0.0, description="voice: silence after the speech end before a command the turn probe judged complete is committed (0: as soon as the verdict and the ASR final are both there)")
+    VWA_SUMMARIZE: bool = Field(False, description="executor: the summarize intent reads the page's title, url and visible text and asks the brain (POST /summarize) for a spoken-style summary (0, the default: the step answers the fixed note it always did and no request is made)")
+    VWA_SUMMARIZE_URL: Optional[str] = Field(None, description="executor -> brain /summarize URL (default: BRAIN_URL with /parse replaced by /summarize)")
+    VWA_SUMMARY_PAGE_CHARS: int = Field(20000, ge=1, description="executor: at most this many characters of the page's visible text are sent to /summarize (the brain cuts further, by tokens, to its context window)")
+    VWA_SUMMARY_MAX_CHARS: int = Field(400, ge=1, le=4096, description="brain: default upper bound of a summary's length in characters (a request's max_chars overrides it; lowered where the model's window leaves no room for it)")
+    VWA_SUMMARY_TEMPERATURE: float = Field(0.7, gt=0.0, description="brain: sampling temperature of summaries. The four summary sampling defaults are the values common for free text; they are policy defaults and are NOT tuned on real weights or real pages")
+    VWA_SUMMARY_TOP_P: float = Field(0.9, gt=0.0, description="brain: nucleus (top-p) mass of summaries, taken over the renormalised top-k (>= 1: no cut)")
+    VWA_SUMMARY_TOP_K: int = Field(50, ge=1, le=1024, description="brain: top-k of summaries (the nucleus kernel sorts at most 1024 candidates)")
+    VWA_SUMMARY_PENALTY: float = Field(1.1, gt=0.0, description="brain: repetition penalty of summaries over the last 64 sampled answer tokens (1: none)")
     VWA_ASR_BUSY_FILE: Optional[str] = Field(None, description="/dev/shm word the voice worker's ASR batcher marks busy while recognition runs (shared-GPU deployment: the brain's decode uses the chained launch only while it is idle; launch.py sets it)")
     VWA_ASR_BUSY_HOLD_MS: float = Field(20.0, description="brain: keep the per-kernel decode form this long after the last ASR pass ended")
     VWA_ENDPOINT_MS: float = Field(300.0, description="trailing silence that ends an utterance (VAD endpoint)")

@@ -49,7 +49,7 @@ import json
 import os
 import time
 from concurrent.futures import ThreadPoolExecutor
-from typing import Any, Callable, Dict, Optional
+from typing import Any, Callable, Dict, List, Optional
 
 import aiohttp
 from aiohttp import WSMsgType, web
@@ -141,6 +141,19 @@ async def post_json_and_return(session: aiohttp.ClientSession, url: str, body: A
         return json.loads(text)
     except ValueError:
         return {"ok": False}
+
+
+def spoken_summaries(resp: Any) -> List[str]:
+    """The summaries in an executor /execute reply: ``data.summary`` of every step where it is a
+    non-empty string, in step order (anything else -- another reply shape, no such step -- gives none)."""
+    results = resp.get("results") if isinstance(resp, dict) else None
+    out = []
+    for step in results if isinstance(results, list) else ():
+        data = step.get("data") if isinstance(step, dict) else None
+        s = data.get("summary") if isinstance(data, dict) else None
+        if isinstance(s, str) and s.strip():
+            out.append(s)
+    return out
 
 
 def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Optional[str] = None,
@@ -325,6 +338,11 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
                 await send({"type": "execution_result",
                             "payload": f"Executed {len(safe)} actions successfully. Session: {st['session_id']}"})
                 m.inc("executions")
+                # a step that carries a summary (the executor's summarize intent with VWA_SUMMARIZE) is
+                # spoken: one tts frame each, after the result
+                for summary in spoken_summaries(resp):
+                    await send({"type": "tts", "payload": summary})
+                    m.inc("summaries_spoken")
             except Exception as e:  # noqa: BLE001
                 await send({"type": "execution_error", "payload": f"Execution failed: {e}"})
                 m.inc("execution_errors")
