@@ -21,6 +21,8 @@
 // the activation fragments are streamed from global memory alongside the weights (X is a few
 // hundred KB and stays L2-resident, so the extra loads hit L2, not HBM), with the same
 // two-register-set pipeline; only the reduction scratch lives in LDS.
+#include <type_traits>
+
 #include "common.h"
 #include "vwa_kernels.h"
 #include "mq_attention.h"
@@ -32,6 +34,19 @@ namespace {
 enum Epi { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_GELU = 3, EPI_QKV = 4 };
 
 constexpr unsigned kOOB = 0xFFFFFFF0u;
+
+// CHAIN_PK_DIAG (never defined by the project's build; tools/pk_diag_build.py compiles a second library
+// with it, selected with VWA_KERNEL_SO): timing cells of the chained launch with WRONG RESULTS by
+// design, like chain_probe.py's --no-wait.  They change arithmetic and load counts only -- every
+// address, wait, barrier and counter is the committed kernel's.
+//   1  packed items go to the MFMAs undecoded (no pack_decode): what the decode costs where it stands
+//   2  a tiled bf16 item issues 13 of its 16 loads (the packed item's bytes without its decode)
+// Such a library holds only the nt Llama tails of GQA group 4 with the QKV phase (what the probe runs).
+#ifndef CHAIN_PK_DIAG
+#define CHAIN_PK_DIAG 0
+#endif
+// loads a tiled bf16 item of 16 registers issues
+constexpr int kItemLoads16 = CHAIN_PK_DIAG == 2 ? 13 : 16;
 
 VWA_DEVICE uint4 bload(__amdgpu_buffer_rsrc_t r, unsigned off) {
   u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
@@ -960,7 +975,9 @@ VWA_DEVICE void chain_load(const SkinnyParams& p, int nb, uint4 (&wr)[R], int it
         const unsigned base = ((T * (unsigned)(p.K / 128) + (unsigned)kg) * 4u) * 1024u + (unsigned)lane * 16u;
         const unsigned vb = ok ? base : kOOB2;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) wr[(nt * U + u) * 4 + s] = bload_w_so<WA>(rw, vb, 1024 * s);
+        for (int s = 0; s < 4; ++s)
+          if ((nt * U + u) * 4 + s < (R == 16 ? kItemLoads16 : R))  // (always, but for CHAIN_PK_DIAG 2)
+            wr[(nt * U + u) * 4 + s] = bload_w_so<WA>(rw, vb, 1024 * s);
       } else {
         const unsigned row = (unsigned)(tile * 16 * NT + nt * 16 + nl);
         const unsigned base = (row * (unsigned)p.K + (unsigned)(kg * 128 + 32 * g)) * 2u;
@@ -1058,8 +1075,9 @@ VWA_DEVICE void chain_preload(const SkinnyParams& p, int nb, const PhaseRange& r
       const unsigned vb = ok ? base : kOOB2;
 #pragma unroll
       for (int s = 0; s < LPK; ++s)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rw, (__attribute__((address_space(3))) void*)(wd + ((nt * U + u) * LPK + s) * 1024), 16, vb, 1024 * s, 0, WA);
+        if (F8 || (nt * U + u) * LPK + s < kItemLoads16)  // (always, but for CHAIN_PK_DIAG 2)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(
+              rw, (__attribute__((address_space(3))) void*)(wd + ((nt * U + u) * LPK + s) * 1024), 16, vb, 1024 * s, 0, WA);
     }
   }
 }
@@ -1213,6 +1231,10 @@ VWA_DEVICE void chain_phase(const ChainParams& cp, int i, uint4 (&X0)[R], uint4 
       if (nw == 2) asm volatile("s_waitcnt vmcnt(34)" ::: "memory");
       else if (nw == 1) asm volatile("s_waitcnt vmcnt(17)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else if constexpr (R == 16 && kItemLoads16 == 13) {  // (CHAIN_PK_DIAG 2: the same wait over 13-load items)
+      if (nw == 2) asm volatile("s_waitcnt vmcnt(26)" ::: "memory");
+      else if (nw == 1) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else if constexpr (R == 16) {
       if (nw == 2) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
       else if (nw == 1) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
@@ -1285,43 +1307,62 @@ VWA_DEVICE void chain_phase(const ChainParams& cp, int i, uint4 (&X0)[R], uint4 
     // (PK) bit j: k-group j = nt * U + u of this item holds a value the code cannot express
     unsigned flagged = 0;
     if constexpr (PK) flagged = (unsigned)__ballot(wr[13].x != 0u);
+    // (PK) A flagged k-group's fragments are loaded here, from the bf16 copy.  With that load behind
+    // a branch per fragment the compiler puts an s_waitcnt vmcnt(0) at every join -- the load is the
+    // youngest in the queue on one side -- and the unflagged side runs into it too: each of the item's
+    // 16 MFMAs then waited for the OTHER register set's item as well, the one issued ahead, and a wave
+    // had one item in flight where the bf16 form has two.  So the item's loop exists twice: `body(false)`
+    // holds no load and gets the bf16 form's counted waits; `body(true)`, taken when any k-group of the
+    // item is flagged (~1 in 10^5), is the loop with the branches.  Same fragments, same MFMA order.
+    auto body = [&](auto slow_t) {
+      constexpr bool SLOW = decltype(slow_t)::value;
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int kg = r.gb + b * U + u;
-      if (kg >= r.ge) break;  // wave-uniform
+      for (int u = 0; u < U; ++u) {
+        const int kg = r.gb + b * U + u;
+        if (kg >= r.ge) break;  // wave-uniform
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        uint4 a = make_uint4(0, 0, 0, 0);
-        if constexpr (XG) a = wr[8 + u * 4 + s];
-        else if (nl < M) a = *reinterpret_cast<const uint4*>(xs + nl * xstride + kg * 128 + 32 * g + 8 * s);
+        for (int s = 0; s < 4; ++s) {
+          uint4 a = make_uint4(0, 0, 0, 0);
+          if constexpr (XG) a = wr[8 + u * 4 + s];
+          else if (nl < M) a = *reinterpret_cast<const uint4*>(xs + nl * xstride + kg * 128 + 32 * g + 8 * s);
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-          if constexpr (F8) {
-            // 8 e4m3 of register (nt, u, s >> 1), half s & 1 -> one bf16 B fragment (k 32 g + 8 s ..);
-            // the per-row scale is applied to the finished column in the epilogue (cs0 / cs1)
-            const uint4 w8 = wr[(nt * U + u) * 2 + (s >> 1)];
-            const unsigned d0 = (s & 1) ? w8.z : w8.x, d1 = (s & 1) ? w8.w : w8.y;
-            uint4 bw;
-            bw.x = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, false));
-            bw.y = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, true));
-            bw.z = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, false));
-            bw.w = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, true));
-            acc[nt] = mfma16(as_bf16x8(a), as_bf16x8(bw), acc[nt]);
-          } else if constexpr (PK) {
-            const int j = nt * U + u;
-            uint4 bw;
-            if ((flagged >> j) & 1u) {  // wave-uniform, ~1 k-group in 10^5: the fragment from the bf16 copy
-              const unsigned T = (unsigned)(((r.u0 + it) / nb) * NT + nt);
-              bw = bload(rw16, ((T * (unsigned)(K / 128) + (unsigned)kg) * 4u + (unsigned)s) * 1024u + (unsigned)lane * 16u);
+          for (int nt = 0; nt < NT; ++nt) {
+            if constexpr (F8) {
+              // 8 e4m3 of register (nt, u, s >> 1), half s & 1 -> one bf16 B fragment (k 32 g + 8 s ..);
+              // the per-row scale is applied to the finished column in the epilogue (cs0 / cs1)
+              const uint4 w8 = wr[(nt * U + u) * 2 + (s >> 1)];
+              const unsigned d0 = (s & 1) ? w8.z : w8.x, d1 = (s & 1) ? w8.w : w8.y;
+              uint4 bw;
+              bw.x = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, false));
+              bw.y = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, true));
+              bw.z = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, false));
+              bw.w = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, true));
+              acc[nt] = mfma16(as_bf16x8(a), as_bf16x8(bw), acc[nt]);
+            } else if constexpr (PK) {
+              const int j = nt * U + u;
+              uint4 bw;
+              if (SLOW && ((flagged >> j) & 1u)) {  // wave-uniform: the fragment from the bf16 copy
+                const unsigned T = (unsigned)(((r.u0 + it) / nb) * NT + nt);
+                bw = bload(rw16, ((T * (unsigned)(K / 128) + (unsigned)kg) * 4u + (unsigned)s) * 1024u + (unsigned)lane * 16u);
+              } else if constexpr (CHAIN_PK_DIAG == 1) {  // raw registers (every loaded one stays in use)
+                bw = wr[j * 3 + (s < 3 ? s : 0)];
+                if (s == 3) bw.x = get_comp(wr[12], j) ^ brep;
+              } else {
+                bw = pack_decode(wr[j * 3 + (s >> 1)], get_comp(wr[j * 3 + 2], s), get_comp(wr[12], j), s, brep);
+              }
+              acc[nt] = mfma16(as_bf16x8(a), as_bf16x8(bw), acc[nt]);
             } else {
-              bw = pack_decode(wr[j * 3 + (s >> 1)], get_comp(wr[j * 3 + 2], s), get_comp(wr[12], j), s, brep);
+              acc[nt] = mfma16(as_bf16x8(a), as_bf16x8(wr[(nt * U + u) * 4 + s]), acc[nt]);
             }
-            acc[nt] = mfma16(as_bf16x8(a), as_bf16x8(bw), acc[nt]);
-          } else {
-            acc[nt] = mfma16(as_bf16x8(a), as_bf16x8(wr[(nt * U + u) * 4 + s]), acc[nt]);
           }
         }
       }
+    };
+    if constexpr (PK) {
+      if (flagged) body(std::true_type{});
+      else body(std::false_type{});
+    } else {
+      body(std::false_type{});
     }
   };
   const int u1 = r.u0 + r.n_items;
@@ -1971,6 +2012,17 @@ extern "C" int vwa_chain_launch(const ChainParams* d_cp, int seq, int n_phases, 
     if (seq != 0 || xg2 || (attn_g != 4 && attn_g != 8) || (n_phases != 3 && n_phases != 4)) return -10;
     if (pk ? (f8 || !o2) : ((f8 != 0) == (o2 != 0))) return -10;
     if (n_layers > 1 && n_phases != 4) return -10;
+#if CHAIN_PK_DIAG
+    if (f8 || attn_g != 4 || n_phases != 4) return -10;
+    if (n_layers > 1) {
+      if (pk) hipLaunchKernelGGL((chain_wnt_kernel<4, 4, false, true, true, true>), dim3(grid), dim3(8 * 64), lds, st, d_cp, n_layers);
+      else hipLaunchKernelGGL((chain_wnt_kernel<4, 4, false, true, true, false>), dim3(grid), dim3(8 * 64), lds, st, d_cp, n_layers);
+    } else {
+      if (pk) hipLaunchKernelGGL((chain_wnt_kernel<4, 4, false, true, false, true>), dim3(grid), dim3(8 * 64), lds, st, d_cp, n_layers);
+      else hipLaunchKernelGGL((chain_wnt_kernel<4, 4, false, true, false, false>), dim3(grid), dim3(8 * 64), lds, st, d_cp, n_layers);
+    }
+    return (int)hipGetLastError();
+#else
 #define VWA_CHAIN_LAUNCH_WNT(N, G, F8_, O2_, MULTI_, PK_) \
   hipLaunchKernelGGL((chain_wnt_kernel<N, G, F8_, O2_, MULTI_, PK_>), dim3(grid), dim3(8 * 64), lds, st, d_cp, n_layers)
 #define VWA_CHAIN_LAUNCH_WNT_G(N, F8_, O2_, MULTI_, PK_) \
@@ -1988,7 +2040,11 @@ extern "C" int vwa_chain_launch(const ChainParams* d_cp, int seq, int n_phases, 
 #undef VWA_CHAIN_LAUNCH_WNT_G
 #undef VWA_CHAIN_LAUNCH_WNT
     return (int)hipGetLastError();
+#endif
   }
+#if CHAIN_PK_DIAG
+  return -10;  // (the diagnostic library holds nothing but the nt launches above)
+#else
   if (pk) {  // packed bf16 weights (SkinnyParams::w_pack): Llama tail with attention, o_proj in 32-column tiles
     if (seq != 0 || f8 || xg2 || !o2 || (attn_g != 4 && attn_g != 8) || (n_phases != 3 && n_phases != 4)) return -10;
     if (n_layers > 1 && n_phases != 4) return -10;
@@ -2082,6 +2138,7 @@ extern "C" int vwa_chain_launch(const ChainParams* d_cp, int seq, int n_phases, 
 #else
   return -10;
 #endif
+#endif  // CHAIN_PK_DIAG
 }
 
 // (round 4's 32-column tiles for the plain epilogues measured slower at
