@@ -309,6 +309,21 @@ class AsrEngine:
         t = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int16)).to(self.model.device, non_blocking=True)
         return ops.pcm16_to_f32(t, in_rate=rate)
 
+    def wire_to_audio(self, raw, fmt) -> torch.Tensor:
+        """A window of wire frames (bytes or a uint8 array, whole frames of ``fmt``: asr/wire.py
+        AudioFormat) -> the 16 kHz f32 samples decode_many takes: one ops.ingest launch (G.711 / PCM16
+        decode, downmix, band-limited resampling)."""
+        a = np.frombuffer(raw, dtype=np.uint8).copy() if isinstance(raw, (bytes, bytearray, memoryview)) else raw
+        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)).to(self.model.device,
+                                                                                      non_blocking=True)
+        out = ops.ingest(t, fmt)
+        if self.ingest_hook is not None:
+            self.ingest_hook(t, fmt, out)
+        return out
+
+    # test hook: called with (raw tensor, fmt, the audio) after every wire_to_audio
+    ingest_hook = None
+
     # ---- device-resident greedy decode (one session): step graph = forward -> masked argmax ->
     # decode_advance (sampled token becomes the next input, position / context / KV slot move on),
     # replayed back to back; the host reads the tokens once per chunk instead of once per token

@@ -2,7 +2,11 @@
 apps/voice/src/deepgram.ts:33-51).
 
 The voice server feeds raw PCM16 LE 16 kHz mono frames (the UI sends ~60 ms packets,
-apps/web/src/App.tsx:279-288).  A session keeps the current utterance buffer and:
+apps/web/src/App.tsx:279-288) -- or, to a session made with a wire format (``fmt=``: asr/wire.py
+AudioFormat, Deepgram's encoding / sample_rate / channels), frames of that format: the window then
+holds the wire bytes, the VAD reads a mono int16 view decoded here, every time below is counted at
+the format's own rate, and the recogniser turns the window into 16 kHz samples on the GPU
+(AsrEngine.wire_to_audio).  A session keeps the current utterance buffer and:
 
 * energy VAD on 20 ms frames tracks speech start and trailing silence;
 * every ``partial_every_s`` of new speech it runs a recognition pass and emits an interim result
@@ -51,6 +55,7 @@ import numpy as np
 
 from .segments import cut_index, ts_time
 from .words import confidence as _confidence
+from .wire import AudioFormat, WireAudio, mono_int16
 from .words import shift_words
 
 
@@ -160,8 +165,16 @@ class StreamingAsrSession:
                  noise_mult: Optional[float] = None, words: Optional[bool] = None, language: Optional[str] = None,
                  no_speech_threshold: Optional[float] = None, beam: Optional[int] = None,
                  alternatives: Optional[int] = None, keyterms=None, longform: Optional[bool] = None,
-                 fallback=None, fallback_reject: Optional[bool] = None):
+                 fallback=None, fallback_reject: Optional[bool] = None, fmt: Optional[AudioFormat] = None):
         from ..utils.env import asr_beam_knobs, knob
+
+        # the wire format (asr/wire.py; None: mono PCM16 at ``rate``, the session as it always was).
+        # With one, the window buffer holds wire frames and the recogniser gets them as a WireAudio
+        # (decoded, mixed and resampled on the GPU: ops.ingest); the session's clock -- start, duration,
+        # endpointing, the window, the long-form cut -- counts frames of the format's own rate
+        self.fmt = fmt
+        if fmt is not None:
+            rate = fmt.sample_rate
 
         # the quality gate and temperature fallback (VWA_ASR_FALLBACK, off by default; asr/fallback.py):
         # a FallbackPolicy, True (the policy of the VWA_ASR_TEMPERATURES / _LOGPROB_THRESHOLD /
@@ -244,7 +257,10 @@ class StreamingAsrSession:
         self.frame = rate // 50  # 20 ms
         # the utterance buffer: preallocated to the window (+ one packet), appended in place --
         # no per-frame re-concatenation of the whole utterance
-        self._pcm = np.zeros(self.max_window + 4 * rate, dtype=np.int16)
+        # (with a wire format: one row of frame bytes per frame, so every index stays a frame count)
+        self._frame_bytes = 2 if fmt is None else fmt.frame_bytes
+        self._pcm = (np.zeros(self.max_window + 4 * rate, dtype=np.int16) if fmt is None
+                     else np.zeros((self.max_window + 4 * rate, fmt.frame_bytes), dtype=np.uint8))
         self._n = 0
         self._carry = b""
         self.t_offset = 0.0          # stream time of buf[0]
@@ -271,13 +287,17 @@ class StreamingAsrSession:
 
     # ------------------------------------------------------------------ internals
     @property
-    def buf(self) -> np.ndarray:
-        """The current utterance's samples (a view of the preallocated buffer)."""
+    def buf(self):
+        """The current utterance's samples (a view of the preallocated buffer); with a wire format,
+        its frames as the WireAudio a recogniser takes."""
+        if self.fmt is not None:
+            return WireAudio(self._pcm[: self._n].reshape(-1), self.fmt)
         return self._pcm[: self._n]
 
     def _append(self, fr: np.ndarray) -> None:
         if self._n + len(fr) > len(self._pcm):  # (never with the window cut; a safety net)
-            self._pcm = np.concatenate([self._pcm, np.zeros(max(len(fr), len(self._pcm) // 2), dtype=np.int16)])
+            more = np.zeros((max(len(fr), len(self._pcm) // 2),) + self._pcm.shape[1:], dtype=self._pcm.dtype)
+            self._pcm = np.concatenate([self._pcm, more])
         self._pcm[self._n : self._n + len(fr)] = fr
         self._n += len(fr)
 
@@ -431,7 +451,7 @@ class StreamingAsrSession:
 
     def _final(self, use_spec: bool = True, speech_final: Optional[bool] = None) -> List[Dict]:
         out: List[Dict] = []
-        if self.speech >= self.min_speech and len(self.buf):
+        if self.speech >= self.min_speech and self._n:
             hyp = None
             if use_spec and self._spec is not None:
                 try:
@@ -475,7 +495,7 @@ class StreamingAsrSession:
                     kw["alternatives"] = alts
             if speech_final is not None:
                 kw["speech_final"] = speech_final
-            out.append(results_event(text, is_final=True, start=self.t_offset, duration=len(self.buf) / self.rate,
+            out.append(results_event(text, is_final=True, start=self.t_offset, duration=self._n / self.rate,
                                      model=self.model_name, **kw, **self._lang_kw(hyp)))
             self.stats["finals"] += 1
         self._reset_utterance()
@@ -498,23 +518,29 @@ class StreamingAsrSession:
             return []
         self.last_partial = hyp.text
         self.stats["partials"] += 1
-        return [results_event(hyp.text, is_final=False, start=self.t_offset, duration=len(self.buf) / self.rate,
+        return [results_event(hyp.text, is_final=False, start=self.t_offset, duration=self._n / self.rate,
                               model=self.model_name, **self._lang_kw(hyp))]
 
     # ------------------------------------------------------------------ API
     def push(self, data: bytes) -> List[Dict]:
         data = self._carry + bytes(data)
-        if len(data) % 2:
-            self._carry, data = data[-1:], data[:-1]
+        odd = len(data) % self._frame_bytes  # a packet that ends inside a frame: its bytes wait for the next
+        if odd:
+            self._carry, data = data[-odd:], data[:-odd]
         else:
             self._carry = b""
-        pcm = np.frombuffer(data, dtype="<i2")
+        if self.fmt is None:
+            pcm = wire = np.frombuffer(data, dtype="<i2")
+        else:
+            # the VAD reads a mono int16 view decoded here; the window keeps the wire frames themselves
+            wire = np.frombuffer(data, dtype=np.uint8).reshape(-1, self._frame_bytes)
+            pcm = mono_int16(data, self.fmt)
         events: List[Dict] = []
         for i in range(0, len(pcm), self.frame):
             fr = pcm[i : i + self.frame]
             if len(fr) == 0:
                 continue
-            self._append(fr)
+            self._append(wire[i : i + self.frame])
             rms = float(np.sqrt(np.mean(fr.astype(np.float32) ** 2)))
             self._track_floor(rms)
             if rms >= max(self.thresh, self.noise_mult * self.noise_floor):
@@ -542,7 +568,7 @@ class StreamingAsrSession:
                 self.since_partial += len(fr)
             if self.speech >= self.min_speech and self.trailing_silence >= self.endpoint:
                 events += self._final()
-            elif len(self.buf) >= self.max_window:
+            elif self._n >= self.max_window:
                 events += self._window_full() if self.longform else self._final(use_spec=False)
             elif (self.spec_at and self._spec is None and self.speech >= self.min_speech
                   and self.trailing_silence >= self.spec_at):
@@ -624,6 +650,14 @@ def _sot_of(eng, i: int) -> Optional[Dict]:
     return sots[i] if sots and i < len(sots) else None
 
 
+def _to_audio(eng, pcm):
+    """A pass's window as the 16 kHz f32 tensor decode_many takes: int16 samples at 16 kHz, or the
+    wire frames of a session with a format (any format: they differ only up to here)."""
+    if isinstance(pcm, WireAudio):
+        return eng.wire_to_audio(pcm.raw, pcm.fmt)
+    return eng.pcm_to_audio(pcm)
+
+
 def _compile_keyterms(eng, keyterms):
     """A pass's ``keyterms=`` as the engine takes it: a compiled set stays, text terms are compiled
     with the engine's tokenizer (cached by content), None or empty is None."""
@@ -670,7 +704,7 @@ class EngineRecognizer:
         if ks is not None:
             kw["keyterms"] = [ks]
         if timestamps:
-            toks = self.eng.decode_many([self.eng.pcm_to_audio(pcm)], max_tokens=_ts_tokens(self.eng),
+            toks = self.eng.decode_many([_to_audio(self.eng, pcm)], max_tokens=_ts_tokens(self.eng),
                                         timestamps=[True], **kw)[0]
             return _ts_hypothesis(self.eng, toks, 0)
         prefix = list(prefix)[: self.eng.max_prefix()]  # the prefix the decoder actually forces
@@ -681,7 +715,7 @@ class EngineRecognizer:
             kw["beam_size"] = int(beam)
         elif fallback is not None:
             kw["fallback"] = fallback
-        toks = self.eng.decode_many([self.eng.pcm_to_audio(pcm)], [prefix], max_tokens=self.max_tokens, **kw)[0]
+        toks = self.eng.decode_many([_to_audio(self.eng, pcm)], [prefix], max_tokens=self.max_tokens, **kw)[0]
         return _hypothesis(self.eng, prefix + toks, len(pcm), self.eng.last_alignments[0] if words else None,
                            _sot_of(self.eng, 0), self.eng.last_beams[0] if beam > 1 else None, prefix,
                            self.eng.last_scores[0] if "fallback" in kw else None)
@@ -777,7 +811,8 @@ class AsrBatcher:
             if self._stop:
                 raise RuntimeError("ASR batcher stopped")
             # (cut to what the decoder forces: the hypothesis is built on the prefix it really used)
-            self._q.append((np.array(pcm, dtype=np.int16, copy=True), list(prefix)[: self.eng.max_prefix()], fut,
+            own = pcm.copy() if isinstance(pcm, WireAudio) else np.array(pcm, dtype=np.int16, copy=True)
+            self._q.append((own, list(prefix)[: self.eng.max_prefix()], fut,
                             bool(words) and self.words, language, beam, ks, bool(timestamps), fallback))
             self._cv.notify()
         return fut
@@ -842,7 +877,7 @@ class AsrBatcher:
         if self.busy is not None:
             self.busy.enter()
         try:
-            audios = [self.eng.pcm_to_audio(item[0]) for item in batch]
+            audios = [_to_audio(self.eng, item[0]) for item in batch]
             max_tokens = _ts_tokens(self.eng) if timestamps else self.max_tokens
             kw = dict(max_tokens=max_tokens)
             if self.tokens_per_s:

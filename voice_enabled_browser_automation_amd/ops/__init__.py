@@ -1180,6 +1180,96 @@ def pcm16_to_f32(pcm: torch.Tensor, in_rate: int = 16000, out: Optional[torch.Te
     return out
 
 
+# ----------------------------------------------------------------------------- wire audio ingest
+INGEST_MAX_CHANNELS = 8          # csrc/ingest/ingest.h kIngestMaxChannels
+INGEST_MAX_FRAMES = 1 << 30      # ... kIngestMaxFrames
+INGEST_PASSBAND = 0.92           # the filter's cutoff as a share of the lower of the two Nyquist rates
+INGEST_KAISER_BETA = 8.0
+ingest_launches = 0              # GPU launches of ingest so far (the tests count them)
+_INGEST_TABLES: dict = {}
+
+
+def ingest_ext():
+    """The wire audio ingest library ``_vwa_ingest.so`` (loaded once). Raises if unavailable."""
+    return _load_lib("_vwa_ingest", "wire audio ingest")
+
+
+def ingest_geometry(rate: int) -> Tuple[int, int, int]:
+    """(L, M, H) of a supported input rate: 16000 / rate = L / M in lowest terms, H = ceil(16 / min(1, L / M))
+    -- the filter reads input samples pos - H + 1 .. pos + H."""
+    from ..asr.wire import AudioFormat
+
+    fmt = AudioFormat(sample_rate=rate)
+    return (*fmt.ratio, fmt.half_taps)
+
+
+def ingest_tables(rate: int, device="cpu") -> torch.Tensor:
+    """The polyphase filter of ``ingest`` for one input rate: f32 [L, 2H], built in f64, rounded once
+    and cached per (rate, device).  Row p, tap k is the weight of input sample pos - H + 1 + k for
+    an output that lies p / L of an input sample past ``pos``: at distance t = k - H + 1 - p / L the
+    Kaiser-windowed sinc  g sinc(g t) I0(8 sqrt(1 - (t / H)^2)) / I0(8),  g = 0.92 min(1, L / M); every
+    row is then scaled to sum 1, so a constant input comes out unchanged at every phase."""
+    dev = torch.device(device)
+    key = (int(rate), str(dev))
+    hit = _INGEST_TABLES.get(key)
+    if hit is not None:
+        return hit
+    L, M, H = ingest_geometry(rate)
+    g = INGEST_PASSBAND * min(1.0, L / M)
+    f64 = torch.float64
+    t = (torch.arange(2 * H, dtype=f64)[None, :] - (H - 1)) - torch.arange(L, dtype=f64)[:, None] / L
+    w = torch.special.i0(INGEST_KAISER_BETA * torch.sqrt((1.0 - (t / H) ** 2).clamp(min=0.0))) \
+        / torch.special.i0(torch.tensor(INGEST_KAISER_BETA, dtype=f64))
+    h = g * torch.sinc(g * t) * w
+    h = h / h.sum(dim=1, keepdim=True)
+    tab = h.float().contiguous().to(dev)
+    _INGEST_TABLES[key] = tab
+    return tab
+
+
+def ingest(raw: torch.Tensor, fmt, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A window of wire bytes -> the 16 kHz f32 mono samples ``log_mel`` reads (csrc/ingest/ingest.h has
+    the arithmetic).  ``raw``: contiguous 1-D uint8, whole frames of ``fmt`` (asr/wire.py AudioFormat:
+    linear16 | mulaw | alaw, 8..48 kHz, 1..8 interleaved channels, their mean or one of them).  ``out``:
+    contiguous f32 [>= n_out], n_out = n_frames * L // M; allocated if None.  16 kHz input passes through
+    unfiltered.  One launch on the GPU, no host synchronisation; host tensors take the torch reference
+    and never load the library.  Returns ``out[:n_out]``."""
+    global ingest_launches
+    from ..asr.wire import AudioFormat
+
+    if not isinstance(fmt, AudioFormat):
+        raise ValueError(f"ingest: fmt must be an AudioFormat, not {type(fmt).__name__}")
+    if not isinstance(raw, torch.Tensor) or raw.dtype != torch.uint8 or raw.dim() != 1 or not raw.is_contiguous():
+        raise ValueError("ingest: raw must be a contiguous 1-D uint8 tensor, not "
+                         f"{getattr(raw, 'dtype', type(raw).__name__)} {tuple(getattr(raw, 'shape', ()))}")
+    if raw.numel() % fmt.frame_bytes:
+        raise ValueError(f"ingest: raw must hold whole frames of {fmt.frame_bytes} bytes, not {raw.numel()} bytes")
+    n_in = raw.numel() // fmt.frame_bytes
+    if n_in > INGEST_MAX_FRAMES:
+        raise ValueError(f"ingest: raw must hold <= {INGEST_MAX_FRAMES} frames, not {n_in}")
+    if fmt.encoding == "linear16" and raw.data_ptr() % 2:
+        raise ValueError("ingest: raw must be 2-byte aligned for linear16")
+    n_out = fmt.n_out(n_in)
+    if out is None:
+        out = torch.empty((n_out,), dtype=torch.float32, device=raw.device)
+    elif out.dtype != torch.float32 or out.dim() != 1 or not out.is_contiguous() or out.numel() < n_out:
+        raise ValueError(f"ingest: out must be contiguous float32 [>= {n_out}], not {out.dtype} {tuple(out.shape)}")
+    elif out.device != raw.device:
+        raise ValueError(f"ingest: out is on {out.device}, raw on {raw.device}")
+    elif n_out and out.data_ptr() < raw.data_ptr() + raw.numel() and raw.data_ptr() < out.data_ptr() + 4 * n_out:
+        raise ValueError("ingest: out must not overlap raw")
+    L, M = fmt.ratio
+    H = fmt.half_taps
+    table = ingest_tables(fmt.sample_rate, raw.device)
+    if not _gpu(raw):
+        return ref.ingest(raw, fmt.encoding, fmt.channels, fmt.channel, L, M, H, table, out)
+    # (a missing library raises: there is no other GPU path)
+    ingest_ext().ingest(raw, fmt.code, fmt.sample_rate, fmt.channels, -1 if fmt.channel is None else fmt.channel,
+                        table, out)
+    ingest_launches += 1
+    return out[:n_out]
+
+
 _LOGMEL_TABLES: dict = {}
 
 

@@ -277,6 +277,54 @@ def pcm16_to_f32(pcm, ratio, out):
     return out
 
 
+def _g711_table(law: str) -> torch.Tensor:
+    """code -> the standard's 16-bit value, int32 [256] (the arithmetic of csrc/ingest/ingest_resample.hip)."""
+    c = torch.arange(256, dtype=torch.int32)
+    if law == "mulaw":
+        u = ~c & 0xFF
+        t = (((u & 0x0F) << 3) + 0x84) << ((u >> 4) & 7)
+        return torch.where((u & 0x80) != 0, 0x84 - t, t - 0x84)
+    a = c ^ 0x55
+    seg = (a >> 4) & 7
+    t = (a & 0x0F) << 4
+    t = torch.where(seg == 0, t + 8, (t + 0x108) << (seg - 1).clamp(min=0))
+    return torch.where((a & 0x80) != 0, t, -t)
+
+
+def ingest(raw, encoding, channels, channel, L, M, H, table, out):
+    """csrc/ingest/ingest.h on host tensors, in its order of operations: decode, x (1 / 32768), the
+    f32 mean in channel order (or the one channel), then per output the 2H taps in ascending order
+    in f32 (a product and a sum per tap, each rounded; the kernel fuses the two).  raw: uint8, whole
+    frames; out: f32 [>= n_in * L // M].  Returns out[:n_out]."""
+    if encoding == "linear16":
+        v = raw.view(torch.int16).to(torch.int32)
+    else:
+        v = _g711_table(encoding)[raw.long()]
+    v = v.reshape(-1, channels).float() * (1.0 / 32768.0)
+    n_in = v.shape[0]
+    if channel is not None:
+        x = v[:, channel]
+    else:
+        x = v[:, 0]
+        for c in range(1, channels):
+            x = x + v[:, c]
+        if channels > 1:
+            x = x / float(channels)
+    n_out = n_in * L // M
+    if L == M:
+        out[:n_out].copy_(x)
+        return out[:n_out]
+    q = torch.arange(n_out, dtype=torch.int64) * M
+    pos = torch.div(q, L, rounding_mode="floor")
+    ph = q - pos * L
+    xp = torch.cat([torch.zeros(H, dtype=torch.float32), x, torch.zeros(H + 1, dtype=torch.float32)])  # x[j] at j + H
+    acc = torch.zeros(n_out, dtype=torch.float32)
+    for k in range(2 * H):
+        acc = acc + table[ph, k] * xp[pos + 1 + k]
+    out[:n_out].copy_(acc)
+    return out[:n_out]
+
+
 def log_mel(audio, *, n_frames, window, mel_fb, out):
     """Whisper log-mel of a padded window -> out bf16 [n_frames, n_mels] (channels-last)."""
     stft = torch.stft(audio.float(), 400, 160, window=window.float(), center=True, pad_mode="reflect",

@@ -29,6 +29,7 @@ from typing import List, Optional
 import aiohttp
 from aiohttp import WSMsgType, web
 
+from ..asr.wire import FormatError, format_from_query
 from ..utils.metrics import Metrics
 from .server import VERSION
 from ..utils.env import knob
@@ -144,9 +145,18 @@ def build_router(worker_urls: List[str], *, probe_s: Optional[float] = None,
             self.move = asyncio.Event()
 
     async def stream(req: web.Request) -> web.WebSocketResponse:
+        m: Metrics = app["metrics"]
+        # a wire format no worker serves (encoding / sample_rate / channels / channel, multichannel:
+        # asr/wire.py) is refused here as a worker refuses it -- HTTP 400 before the upgrade; behind an
+        # upgraded client the worker's 400 would look like a dead worker and start a failover
+        try:
+            format_from_query(req.query)
+        except FormatError as e:
+            m.inc("asr_wire_rejected")
+            return web.json_response({"error": "unsupported_audio_format", "param": e.param, "message": str(e)},
+                                     status=400)
         ws = web.WebSocketResponse()
         await ws.prepare(req)
-        m: Metrics = app["metrics"]
         m.inc("connections")
         client = _Client()
         worker = pick()

@@ -33,7 +33,14 @@ Per connection:
     -- repeated parameters, an optional ``:boost`` suffix in (0, 20] (a trailing ``:number`` is always
     the boost: the term "10:30" is written ``10:30:2``), at most 100 terms -- names words
     the recogniser should prefer (asr/keyterms.py); ``VWA_ASR_KEYTERMS`` gives every session default
-    terms.  Bad input is answered with a ``warn`` frame and the connection goes on.
+    terms.  Bad input is answered with a ``warn`` frame and the connection goes on;
+  * the wire format as Deepgram's ``encoding`` / ``sample_rate`` / ``channels`` options:
+    ``/stream?encoding=mulaw&sample_rate=8000``, ``?encoding=linear16&sample_rate=48000&channels=2``
+    -- linear16 | mulaw | alaw, 8000..48000 Hz (asr/wire.py SAMPLE_RATES), 1..8 interleaved channels
+    whose mean is recognised, or the one channel an optional ``channel=i`` names.  Without them the
+    binary frames are PCM16 LE 16 kHz mono as ever.  An unsupported value, or ``multichannel=true``
+    (per-channel transcripts are not served), is refused with HTTP 400 before the upgrade:
+    ``{"error": "unsupported_audio_format", "param": <the parameter>, "message": ...}``.
 
 Races of the reference fixed here: brain calls of one connection are serialised
 by a per-connection lock (context updates apply in utterance order), and its executor calls run
@@ -54,6 +61,7 @@ from typing import Any, Callable, Dict, List, Optional
 import aiohttp
 from aiohttp import WSMsgType, web
 
+from ..asr.wire import FormatError, format_from_query
 from ..utils.context import merge_context
 from ..utils.metrics import Metrics
 from ..utils.env import knob
@@ -123,14 +131,18 @@ def default_keyterms():
     return [parse_keyterm(x) for x in raw.split(",") if x.strip()][:MAX_KEYTERMS]
 
 
-def _takes_keyterms(factory) -> bool:
+def _takes(factory, keyword: str) -> bool:
     import inspect
 
     try:
         ps = inspect.signature(factory).parameters
     except (TypeError, ValueError):
         return False
-    return "keyterms" in ps or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in ps.values())
+    return keyword in ps or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in ps.values())
+
+
+def _takes_keyterms(factory) -> bool:
+    return _takes(factory, "keyterms")
 
 
 async def post_json_and_return(session: aiohttp.ClientSession, url: str, body: Any) -> Any:
@@ -222,10 +234,23 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
         return web.json_response(snap)
 
     async def stream(req: web.Request) -> web.WebSocketResponse:
+        m: Metrics = app["metrics"]
+        # the wire format (Deepgram's encoding / sample_rate / channels, and our channel=i): refused
+        # before the upgrade when it is not served -- a client must not stream audio nobody decodes
+        try:
+            fmt = format_from_query(req.query)
+            if fmt is not None and asr_factory is not None and not _takes(asr_factory, "fmt"):
+                raise FormatError("encoding", "this recognizer takes mono linear16 at 16000 Hz only")
+        except FormatError as e:
+            m.inc("asr_wire_rejected")
+            return web.json_response({"error": "unsupported_audio_format", "param": e.param, "message": str(e)},
+                                     status=400)
         ws = web.WebSocketResponse()
         await ws.prepare(req)
-        m: Metrics = app["metrics"]
         m.inc("connections")
+        fmt_kw = {} if fmt is None else {"fmt": fmt}
+        if fmt is not None:
+            m.inc(f'asr_wire_sessions{{encoding="{fmt.encoding}",sample_rate="{fmt.sample_rate}"}}')
         loop = asyncio.get_running_loop()
         # per-utterance span (monotonic): first audio -> final transcript -> brain reply
         # pending: final text not yet sent to the brain; spec: a speculative brain call {text, ctx,
@@ -261,14 +286,14 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
             try:
                 if keyterms and _takes_keyterms(asr_factory):
                     try:
-                        asr = asr_factory(keyterms=keyterms)
+                        asr = asr_factory(keyterms=keyterms, **fmt_kw)
                     except ValueError as e:  # (a term the tokenizer cannot take: serve without)
                         kt_warns.append(str(e))
-                        asr = asr_factory()
+                        asr = asr_factory(**fmt_kw)
                 else:
                     if keyterms:
                         kt_warns.append("keyterms are not supported by this recognizer")
-                    asr = asr_factory()
+                    asr = asr_factory(**fmt_kw)
             except Exception as e:  # noqa: BLE001
                 print(f"[voice] recognizer start failed: {e}", flush=True)
                 m.inc("asr_connect_failed")
@@ -551,6 +576,8 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
             async for msg in ws:
                 if msg.type == WSMsgType.BINARY:
                     m.inc("audio_frames")
+                    if fmt is not None:
+                        m.inc("asr_wire_bytes", len(msg.data))
                     if st["t_utt"] is None:
                         st["t_utt"] = time.perf_counter()
                     if asr is not None:
@@ -649,9 +676,9 @@ def asr_factory_from_env() -> Optional[Callable[[], Any]]:
 
     default_keyterms()  # (a bad VWA_ASR_KEYTERMS stops the worker here)
 
-    def factory(keyterms=None):
+    def factory(keyterms=None, fmt=None):
         return StreamingAsrSession(batcher, model_name=name, partial_every_s=every, beam=beam, alternatives=n_alt,
-                                   keyterms=keyterms)
+                                   keyterms=keyterms, fmt=fmt)
 
     factory.batcher = batcher
     return factory
