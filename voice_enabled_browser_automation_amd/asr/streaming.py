@@ -62,7 +62,8 @@ from .words import shift_words
 def results_event(text: str, *, is_final: bool, start: float, duration: float, model: str,
                   confidence: float = 0.0, words: Optional[List[Dict]] = None, language: Optional[str] = None,
                   language_confidence: Optional[float] = None, no_speech_prob: Optional[float] = None,
-                  alternatives: Optional[List[Dict]] = None, speech_final: Optional[bool] = None) -> Dict:
+                  alternatives: Optional[List[Dict]] = None, speech_final: Optional[bool] = None,
+                  logprobs: Optional[List[float]] = None) -> Dict:
     """``words``: the alternative's Deepgram word list ({"word", "punctuated_word", "start", "end",
     "confidence"}, stream-clock seconds); None: the empty list.  ``language``: the detected (or
     set) language code -- Deepgram's ``channel.detected_language`` / ``language_confidence`` and
@@ -70,7 +71,10 @@ def results_event(text: str, *, is_final: bool, start: float, duration: float, m
     (``metadata.no_speech_prob``).  ``alternatives``: the ranked hypotheses after the first
     ({"transcript", "confidence"}, from a beam pass) -- ``channel.alternatives[1:]`` in Deepgram's
     shape, with no words.  ``speech_final``: a final of a long utterance cut at a segment end says
-    False -- the speaker has not stopped (None: as ``is_final``).  Without them the event is unchanged."""
+    False -- the speaker has not stopped (None: as ``is_final``).  ``logprobs``: the acoustic sum
+    log-probability of every alternative, the first included (a beam final of a session that rescores:
+    the brain's n-best rescoring weighs it against its own score) -- alternative i then carries
+    ``"logprob"``.  Without them the event is unchanged."""
     ev = {
         "type": "Results",
         "channel_index": [0, 1],
@@ -91,6 +95,9 @@ def results_event(text: str, *, is_final: bool, start: float, duration: float, m
     for alt in alternatives or []:
         ev["channel"]["alternatives"].append({"transcript": alt["transcript"], "confidence": alt["confidence"],
                                               "words": []})
+    if logprobs is not None:
+        for alt, lp in zip(ev["channel"]["alternatives"], logprobs):
+            alt["logprob"] = float(lp)
     return ev
 
 
@@ -102,7 +109,8 @@ class Hypothesis:
     logits, the language the pass decoded under, its probability and the probability that the
     window holds no speech; from a beam pass, the ranked hypotheses after the first
     (``alternatives``: {"transcript", "confidence" = exp(avg_logprob)}) -- ``confidence`` is then
-    the best hypothesis' exp(avg_logprob) unless the words pass set it; from a timestamp pass,
+    the best hypothesis' exp(avg_logprob) unless the words pass set it, and ``beam_logprobs`` the
+    ranked hypotheses' sum log-probabilities, the first included; from a timestamp pass,
     ``tokens`` holds the timestamp tokens too and ``segments`` the transcript's segments
     (asr/segments.py: {start, end, tokens, text}, seconds from the window's start); from a pass under
     the quality gate (``fallback=``), ``score``: the engine's score entry of the returned attempt
@@ -116,6 +124,7 @@ class Hypothesis:
     language_confidence: Optional[float] = None
     no_speech_prob: Optional[float] = None
     alternatives: List[Dict] = field(default_factory=list)
+    beam_logprobs: List[float] = field(default_factory=list)
     segments: List[Dict] = field(default_factory=list)
     score: Optional[Dict] = None
 
@@ -165,7 +174,8 @@ class StreamingAsrSession:
                  noise_mult: Optional[float] = None, words: Optional[bool] = None, language: Optional[str] = None,
                  no_speech_threshold: Optional[float] = None, beam: Optional[int] = None,
                  alternatives: Optional[int] = None, keyterms=None, longform: Optional[bool] = None,
-                 fallback=None, fallback_reject: Optional[bool] = None, fmt: Optional[AudioFormat] = None):
+                 fallback=None, fallback_reject: Optional[bool] = None, fmt: Optional[AudioFormat] = None,
+                 rescore: Optional[bool] = None):
         from ..utils.env import asr_beam_knobs, knob
 
         # the wire format (asr/wire.py; None: mono PCM16 at ``rate``, the session as it always was).
@@ -215,6 +225,10 @@ class StreamingAsrSession:
         # final event carries (VWA_ASR_ALTERNATIVES, 1..beam): the final pass and the speculative
         # final pass are asked for recognize(..., beam=W); partials never are
         self.beam, self.n_alternatives = asr_beam_knobs(beam, alternatives)
+        # n-best rescoring (VWA_RESCORE, off by default): only then does every alternative of a beam
+        # final, the first included, carry "logprob", its sum log-probability -- what the voice service
+        # weighs against the brain's language-model score.  Off: the events are what they always were
+        self.rescore = bool(knob("VWA_RESCORE")) if rescore is None else bool(rescore)
 
         # language (VWA_ASR_LANGUAGE): a code, or "auto" -- then the passes of an utterance ask the
         # recognizer for "auto" until the first pass that commits tokens by local agreement; that
@@ -493,6 +507,9 @@ class StreamingAsrSession:
                 alts = list(getattr(hyp, "alternatives", None) or [])[: self.n_alternatives - 1]
                 if alts:
                     kw["alternatives"] = alts
+                    lps = list(getattr(hyp, "beam_logprobs", None) or [])[: len(alts) + 1]
+                    if self.rescore and len(lps) == len(alts) + 1:
+                        kw["logprobs"] = lps
             if speech_final is not None:
                 kw["speech_final"] = speech_final
             out.append(results_event(text, is_final=True, start=self.t_offset, duration=self._n / self.rate,
@@ -617,6 +634,7 @@ def _hypothesis(eng, full: List[int], n_samples: int, al=None, sot: Optional[Dic
         hyp.confidence = math.exp(beams[0]["avg_logprob"])
         hyp.alternatives = [dict(transcript=eng.tok.decode(list(prefix) + list(h["tokens"])).strip(),
                                  confidence=math.exp(h["avg_logprob"])) for h in beams[1:]]
+        hyp.beam_logprobs = [float(h["sum_logprob"]) for h in beams]
     if al is not None:
         hyp.words, hyp.confidence = eng.words_of(al, duration=n_samples / 16000.0), _confidence(al.logprobs)
     if sot is not None:

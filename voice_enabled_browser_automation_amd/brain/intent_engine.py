@@ -25,7 +25,12 @@ grammar-constrained decoding:
   parameters (temperature, top-p, top-k, repetition penalty over its own sampled tokens).  Its rows
   are sampled rows after the parse rows; an iteration that holds one runs one ``ops.nucleus_step``
   launch over all sampled rows in front of the sampler (parse rows pass through), an iteration
-  without one launches exactly what it did before.
+  without one launches exactly what it did before;
+* **rescoring** (``rescore`` / ``rescore_async`` / ``submit_rescore``): a request of a fourth kind that
+  scores the recogniser's n-best alternatives.  Each distinct alternative is one sequence whose prompt
+  is the turn probe's; the ids all alternatives share are prefilled, every id after them rides in the
+  ragged step as a row with a logits row, and one ``ops.seq_logprob`` call per iteration turns those
+  rows into per-sequence running sums on the device -- nothing is decoded, nothing is sampled.
 
 `FakeIntentEngine` is the test double (the reference mocks callLLMJSON with vi.spyOn,
 apps/brain/test/parse.test.ts:7-21).
@@ -45,7 +50,7 @@ import torch
 
 from .. import ops
 from ..grammar import CompiledGrammar, intent_grammar, summary_grammar
-from .prompt import llama3_chat, messages_for, summary_messages, turn_tail
+from .prompt import llama3_chat, messages_for, summary_messages, turn_tail, turn_text
 
 
 class IntentEngineError(RuntimeError):
@@ -75,6 +80,7 @@ class IntentRequest:
     future: Any = None
     diag: Optional[str] = None
     kind: str = "parse"                 # "turn": a turn-completion probe (no matcher, nothing sampled)
+                                        # "score": one alternative of a rescore (the same, many rows)
     probe_text: Optional[str] = None    # "summary": free text under the summary grammar
     result: Optional[Dict[str, Any]] = None
     head_len: int = 0                   # tokens of this request's static head: what _finish publishes
@@ -87,6 +93,18 @@ class IntentRequest:
     page_tokens: int = 0
     truncated: bool = False
     n_kept: int = 0
+    # rescoring: a "score" request is one distinct alternative of its parent (kind "rescore", never
+    # queued itself); its slot in the running-sum buffers, the rows of it scored so far
+    parent: Any = None
+    alt: int = 0
+    slot: int = -1
+    n_scored: int = 0
+    texts: Optional[List[str]] = None       # parent: the texts as given, their normalised forms,
+    norm: Optional[List[str]] = None        # the distinct ones' ids, the common prefix length,
+    alt_ids: Optional[List[List[int]]] = None   # the children and how many are still to retire
+    common: int = 0
+    children: Optional[List["IntentRequest"]] = None
+    left: int = 0
 
     def stats(self, t_end: float) -> Dict[str, Any]:
         return dict(prompt_tokens=len(self.ids), cached_prefix_tokens=self.cached,
@@ -135,9 +153,10 @@ class LLMIntentEngine:
         pin = dev.type == "cuda"
         self._cuda_index = (dev.index if dev.index is not None else torch.cuda.current_device()) if pin else None
         R, W = self.max_active, self.grammar.words
-        self.h_mask = torch.zeros(R, W, dtype=torch.int32, pin_memory=pin)
+        # (one mask row per sampled request and probe, and one per row of a rescored alternative)
+        self.h_mask = torch.zeros(R + self.max_rows, W, dtype=torch.int32, pin_memory=pin)
         self.h_mask_np = self.h_mask.numpy()
-        self.d_mask = torch.zeros(R, W, dtype=torch.int32, device=dev)
+        self.d_mask = torch.zeros(R + self.max_rows, W, dtype=torch.int32, device=dev)
         self.d_temp = torch.full((R,), float(temperature), dtype=torch.float32, device=dev)
         self.d_seed = torch.tensor([seed], dtype=torch.int64, device=dev)
         self.d_step = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -190,6 +209,23 @@ class LLMIntentEngine:
         self.last_summary_trace: List[Dict[str, Any]] = []
         self.last_summary_stats: Dict[str, Any] = {}
         self.summary_stats = dict(summaries=0, summary_tokens=0, n_kept_sum=0, nucleus_launches=0)
+        # rescoring: (target, seq) per scored row staged in pinned memory; the rows' log-probabilities;
+        # three buffers of running sums, one slot per sequence being scored -- d_acc[0] holds the verified
+        # sums, an iteration's calls write the other two in turn and the last one written becomes d_acc[0]
+        # once the step is verified; the traced-run record (off by default)
+        S = ops.RESCORE_MAX_SEQ
+        self.h_score = torch.zeros(2, self.max_rows, dtype=torch.int32, pin_memory=pin)
+        self.d_score = torch.zeros(2, self.max_rows, dtype=torch.int32, device=dev)
+        self.h_score_np = self.h_score.numpy()
+        self.d_lp = torch.zeros(self.max_rows, dtype=torch.float32, device=dev)
+        self.d_acc = [torch.zeros(S, dtype=torch.float32, device=dev) for _ in range(3)]
+        self.h_acc = torch.zeros(S, dtype=torch.float32, pin_memory=pin)
+        self._score_free = list(range(S - 1, -1, -1))
+        self._score_last = 0
+        self.keep_rescore_trace = False
+        self._score_traced = 0
+        self.last_rescore_trace: List[Dict[str, Any]] = []
+        self.last_rescore_stats: Dict[str, Any] = {}
         self.waiting: Deque[IntentRequest] = deque()
         self.active: List[IntentRequest] = []
         self._lock = threading.Lock()
@@ -233,7 +269,7 @@ class LLMIntentEngine:
     def _admit(self, r: IntentRequest) -> None:
         """Admit one request on its own (prefill included)."""
         self._admit_begin(r)
-        self.engine.prefill(r.seq, upto=len(r.ids) - 1)
+        self.engine.prefill(r.seq, upto=self._prefill_upto(r))
         self._admit_end(r)
 
     def _admit_begin(self, r: IntentRequest) -> None:
@@ -244,6 +280,11 @@ class LLMIntentEngine:
         r.t_start = time.perf_counter()
         if r.kind == "turn":
             r.ids = self._encode_head_tail(*turn_tail(r.probe_text, self.chat_format))
+        elif r.kind == "score":
+            if r.parent.alt_ids is None:
+                self._rescore_prepare(r.parent)
+            r.ids = r.parent.alt_ids[r.alt]
+            self._head_len = r.parent.head_len
         elif r.kind == "summary":
             self._encode_summary(r)
         else:
@@ -255,11 +296,22 @@ class LLMIntentEngine:
         r.head_len = self._head_len
         r.seq = eng.new_sequence(r.ids)
         r.cached = r.seq.n_computed
-        if r.cached >= len(r.ids):  # whole prompt cached: recompute its last token for logits
-            r.seq.n_computed = r.cached = len(r.ids) - 1
+        if r.cached >= self._prefill_upto(r) + 1:  # whole prompt cached: recompute its last token for logits
+            r.seq.n_computed = r.cached = self._prefill_upto(r)
+        if r.kind == "score":
+            r.slot = self._score_free.pop()
+            self.d_acc[0][r.slot : r.slot + 1].zero_()  # (on the step's stream, before any call reads it)
+
+    def _prefill_upto(self, r: IntentRequest) -> int:
+        """How many of the prompt's tokens the admission prefill computes: all but the last -- of a
+        rescored alternative, all but the last one it shares with the others (the rest are scored rows)."""
+        return (r.parent.common if r.kind == "score" else len(r.ids)) - 1
 
     def _admit_end(self, r: IntentRequest) -> None:
         r.t_first = time.perf_counter()
+        if r.kind == "score":
+            r.feed = list(r.ids[r.parent.common - 1 :])  # every one of them is a scored row
+            return
         r.feed = [r.ids[-1]]  # the last prompt token joins the batched step
         if r.kind != "turn":
             self._jump_forward(r)
@@ -267,7 +319,7 @@ class LLMIntentEngine:
     def _finish(self, r: IntentRequest, error: Optional[BaseException] = None) -> None:
         r.done = True
         r.error = error
-        if error is None and r.kind != "turn":
+        if error is None and r.kind not in ("turn", "score"):
             r.text = r.out.decode("utf-8")
         if r.seq is not None:
             # only the static system + few-shot prefix is shared across requests; the request's
@@ -275,6 +327,9 @@ class LLMIntentEngine:
             self.engine.free_sequence(r.seq, publish_upto=r.head_len)
             r.seq = None
         r.t_end = time.perf_counter()
+        if r.kind == "score":
+            self._rescore_retired(r, error)  # the parent holds the future
+            return
         if r.kind == "turn":
             if r.result is not None:
                 r.result["ms"] = (r.t_end - r.t_submit) * 1e3
@@ -316,6 +371,8 @@ class LLMIntentEngine:
             with self._lock:
                 if not self.waiting:
                     break
+                if self.waiting[0].kind == "score" and not self._score_free:
+                    break  # every running-sum slot is taken: it waits for a sequence to retire
                 r = self.waiting.popleft()
             try:
                 self._admit_begin(r)
@@ -328,7 +385,7 @@ class LLMIntentEngine:
             # token, which joins the decode step below)
             ta = time.perf_counter()
             try:
-                self.engine.prefill_batch([(r.seq, len(r.ids) - 1) for r in admitted])
+                self.engine.prefill_batch([(r.seq, self._prefill_upto(r)) for r in admitted])
                 self.timing["admit_prefill_ms"] += (time.perf_counter() - ta) * 1e3
             except Exception as e:  # noqa: BLE001
                 if getattr(getattr(self.engine.model, "tp", None), "size", 1) > 1:
@@ -351,9 +408,13 @@ class LLMIntentEngine:
         probes: List[IntentRequest] = []
         # summaries are sampled rows after the parse rows: the parse rows keep their row indices, mask
         # rows and (with the one sampler launch per iteration) the sampler's step counter
+        # rescored alternatives go last: every row of theirs is a logits row (it is scored, not
+        # sampled), after the probes', so that parse, summary and probe rows keep the indices, mask rows
+        # and sampler step counter they would have had without them.  (request, first row, rows) each.
+        pieces: List[Tuple[IntentRequest, int, int]] = []
         order = self.active
         if any(r.kind != "parse" for r in order):
-            order = [r for k in ("parse", "summary", "turn") for r in order if r.kind == k]
+            order = [r for k in ("parse", "summary", "turn", "score") for r in order if r.kind == k]
         for r in order:
             if not r.feed or budget <= 0:
                 continue
@@ -363,19 +424,23 @@ class LLMIntentEngine:
             rows += [(r.seq, t) for t in take]
             budget -= len(take)
             r.feed = r.feed[len(take):]
-            if not r.feed:
+            if r.kind == "score":
+                pieces.append((r, len(rows) - len(take), len(take)))
+            elif not r.feed:
                 last.append(len(rows) - 1)
                 (probes if r.kind == "turn" else batch).append(r)
         if not rows:
             return finished
+        q = sum(k for _, _, k in pieces)
+        sel = last + [i for _, at, k in pieces for i in range(at, at + k)] if pieces else last
         tm = self.timing
         t0 = time.perf_counter()
-        if last and not batch:
-            # probes only: no sampler runs, so no fail word reports a chained launch that timed out
-            # -- the step is verified (and, if need be, re-run) synchronously
-            self.engine.run_rows(rows, logits_for=last, check=True, defer_head=True)
-        elif last:
-            self.engine.run_rows(rows, logits_for=last, check=False, defer_head=True)
+        if sel and not batch:
+            # probes (and scored rows) only: no sampler runs, so no fail word reports a chained launch
+            # that timed out -- the step is verified (and, if need be, re-run) synchronously
+            self.engine.run_rows(rows, logits_for=sel, check=True, defer_head=True)
+        elif sel:
+            self.engine.run_rows(rows, logits_for=sel, check=False, defer_head=True)
         else:
             # only part of one long feed fits this iteration: its rows still have to reach the KV
             # cache (nothing is sampled -- no LM head -- so the step is verified synchronously)
@@ -385,23 +450,27 @@ class LLMIntentEngine:
         self.batch_stats["iterations"] += 1
         self.batch_stats["rows"] += len(rows)
         self.batch_stats["max_active"] = max(self.batch_stats["max_active"], len(self.active))
-        if not batch and not probes:
+        if not batch and not probes and not pieces:
             return finished
         n, p = len(batch), len(probes)
         for i, r in enumerate(batch):  # CPU grammar masks overlap the in-flight forward
             r.matcher.fill_mask(self.h_mask_np[i])
-        if p:
-            # a probe reads every column of its row: its mask row is all ones and counts in
-            # mask_rows, so the masked LM head skips no vocab tile (a skipped tile's logits are stale)
-            self.h_mask_np[n : n + p] = -1
+        if p + q:
+            # a probe reads every column of its row, and so does a scored row: its mask row is all ones
+            # and counts in mask_rows, so the masked LM head skips no vocab tile (a skipped tile's
+            # logits are stale)
+            self.h_mask_np[n : n + p + q] = -1
         t2 = time.perf_counter()
         if not self.zero_copy:
-            self.d_mask[: n + p].copy_(self.h_mask[: n + p], non_blocking=True)
+            self.d_mask[: n + p + q].copy_(self.h_mask[: n + p + q], non_blocking=True)
         mask = self.h_mask if self.zero_copy else self.d_mask
         # the LM head under the same masks: only vocab tiles some row may sample are computed
-        logits = self.engine.head_logits(col_mask=mask if self.masked_head else None, mask_rows=n + p, gather=False)
+        logits = self.engine.head_logits(col_mask=mask if self.masked_head else None, mask_rows=n + p + q,
+                                         gather=False)
         if p:
             self._probe_launch(logits, n, p)  # (before the sampler, on the same stream)
+        if q:
+            self._score_launch(logits, n + p, pieces)  # (likewise; from the verified sums, out of place)
         ns = sum(r.kind == "summary" for r in batch)
         if ns:
             # one nucleus launch over all sampled rows, in front of the sampler (parse rows pass
@@ -425,8 +494,14 @@ class LLMIntentEngine:
             toks = self._sample(logits[:n], n, None, narrowed=bool(ns))
             if p:
                 self._probe_launch(logits, n, p)  # the probes too, from the re-run logits
+            if q:
+                # and the scored rows, from the same sums the failed launch started from: nothing of
+                # it is kept, nothing counts twice
+                self._score_launch(logits, n + p, pieces, rerun=True)
         if p:
             self._probe_finish(probes, logits, n, finished)
+        if q:
+            self._score_finish(pieces, finished)  # the step is verified: its sums become the sums
         self.engine.host_synced()  # the sampled tokens are back: the step's staging copy has run
         t4 = time.perf_counter()
         tm["mask_ms"] += (t2 - t1) * 1e3
@@ -717,6 +792,154 @@ class LLMIntentEngine:
             raise r.error
         return r.result
 
+    # ------------------------------------------------------------------ n-best rescoring
+    def _rescore_prepare(self, par: IntentRequest) -> None:
+        """The ids of every distinct alternative -- exactly a turn probe's -- and the length of their
+        longest common prefix (at most the shortest): what lies inside it has the same probability
+        under every alternative and is not scored."""
+        ids = [self._encode_head_tail(*turn_tail(c.probe_text, self.chat_format)) for c in par.children]
+        par.head_len = self._head_len
+        c, m = 0, min(len(x) for x in ids)
+        while c < m and all(x[c] == ids[0][c] for x in ids):
+            c += 1
+        par.alt_ids, par.common = ids, c
+
+    def _score_launch(self, logits: torch.Tensor, base: int, pieces: List[Tuple[IntentRequest, int, int]],
+                      rerun: bool = False) -> None:
+        """One ops.seq_logprob call (256 rows per piece at most) over the scored rows' logits rows
+        [base, base + q): row p of a sequence carries target ids[p + 1], its last row -1 (the end set);
+        seq is the sequence's slot.  The sums start from d_acc[0], the verified ones, and land in another
+        buffer (``_score_last``): a re-run after a failed chained launch starts from d_acc[0] again."""
+        hv = self.h_score_np
+        j = 0
+        for r, _, k in pieces:
+            pos = r.parent.common - 1 + r.n_scored  # the position of this piece's first row
+            nxt = r.ids[pos + 1 : pos + 1 + k]
+            hv[0, j : j + k] = nxt + [-1] * (k - len(nxt))
+            hv[1, j : j + k] = r.slot
+            j += k
+        q = j
+        self.d_score.copy_(self.h_score, non_blocking=True)
+        V, S, step = logits.shape[1], ops.RESCORE_MAX_SEQ, ops.RESCORE_MAX_ROWS
+        trace = self.keep_rescore_trace
+        if trace and rerun and self._score_traced:  # the failed launch's records describe logits nobody kept
+            del self.last_rescore_trace[-self._score_traced :]
+        self._score_traced = 0
+        src = 0
+        for n_call, i in enumerate(range(0, q, step)):
+            e = min(q, i + step)
+            dst = 1 + (n_call & 1)
+            ops.seq_logprob(logits[base + i : base + e], V, self.d_score[0, i:e], self.end_set(), self.d_score[1, i:e],
+                            S, acc_in=self.d_acc[src], lp=self.d_lp[i:e], acc_out=self.d_acc[dst])
+            if trace:
+                reqs = [r for r, _, _ in pieces]
+                self.last_rescore_trace.append(dict(
+                    texts=[r.probe_text for r in reqs], ids=[list(r.ids) for r in reqs], slots=[r.slot for r in reqs],
+                    first_pos=[r.parent.common - 1 + r.n_scored for r in reqs], counts=[k for _, _, k in pieces],
+                    rows=list(range(base + i, base + e)), target=self.h_score[0, i:e].clone(),
+                    seq=self.h_score[1, i:e].clone(), logits=logits[base + i : base + e].detach().cpu().clone(),
+                    set=self.end_set().cpu().clone(), acc_in=self.d_acc[src].cpu().clone(),
+                    lp=self.d_lp[i:e].cpu().clone(), acc_out=self.d_acc[dst].cpu().clone()))
+                self._score_traced += 1
+            src = dst
+        self._score_last = src
+
+    def _score_finish(self, pieces: List[Tuple[IntentRequest, int, int]], finished: List[IntentRequest]) -> None:
+        """The step is verified: the sums it wrote become the verified ones, and the sequences whose last
+        row it scored retire in this iteration.  The host reads only after the stream is synchronised
+        (see ``_probe_finish``); the synchronise also frees the pinned (target, seq) rows for the next
+        iteration."""
+        a = self.d_acc
+        a[0], a[self._score_last] = a[self._score_last], a[0]
+        done = []
+        for r, _, k in pieces:
+            r.n_scored += k
+            self.batch_stats["rescore_rows"] = self.batch_stats.get("rescore_rows", 0) + k
+            if not r.feed:
+                done.append(r)
+        if self.dev.type == "cuda":
+            if done:
+                self.h_acc.copy_(a[0], non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            out = self.h_acc
+        else:
+            out = a[0]
+        for r in done:
+            r.result = float(out[r.slot])
+            self._finish(r)  # frees the sequence; only the static head is published
+            finished.append(r)
+
+    def _rescore_retired(self, r: IntentRequest, error: Optional[BaseException]) -> None:
+        """A scored sequence left (``_finish``): its slot is free again; the parent resolves with its last."""
+        if r.slot >= 0:
+            self._score_free.append(r.slot)
+            r.slot = -1
+        par = r.parent
+        par.left -= 1
+        if error is not None and par.error is None:
+            par.error = error
+        if par.left:
+            return
+        par.done = True
+        par.t_end = time.perf_counter()
+        if par.error is None:
+            by = {c.probe_text: c for c in par.children}
+            of = [by[t] for t in par.norm]
+            par.result = dict(scores=[c.result for c in of], scored_tokens=[c.n_scored for c in of],
+                              common_prefix_tokens=par.common, prompt_tokens=[len(c.ids) for c in of],
+                              cached_prefix_tokens=min(c.cached for c in par.children),
+                              ms=(par.t_end - par.t_submit) * 1e3)
+            self.last_rescore_stats = par.result
+            self.batch_stats["rescores"] = self.batch_stats.get("rescores", 0) + 1
+        if par.future is not None:
+            if par.error is None:
+                par.future.set_result(par.result)
+            else:
+                par.future.set_exception(par.error)
+
+    def submit_rescore(self, texts: List[str], future=None) -> IntentRequest:
+        """Queue the rescoring of 1..8 alternatives: one sequence per distinct normalised text, admitted
+        like any request.  Returns the parent request (done when its last sequence has retired)."""
+        if getattr(getattr(self.engine.model, "tp", None), "size", 1) > 1:
+            raise IntentEngineError("rescoring is not supported under tensor parallelism (vocab-parallel logits)")
+        if not isinstance(texts, (list, tuple)) or not 1 <= len(texts) <= 8 \
+                or not all(isinstance(t, str) for t in texts):
+            raise IntentEngineError("rescore: texts must be a list of 1..8 strings")
+        norm = [turn_text(t) for t in texts]
+        now = time.perf_counter()
+        par = IntentRequest(messages=[], t_submit=now, future=future, kind="rescore", texts=list(texts), norm=norm)
+        par.children = [IntentRequest(messages=[], t_submit=now, kind="score", probe_text=t, parent=par, alt=i)
+                        for i, t in enumerate(dict.fromkeys(norm))]
+        par.left = len(par.children)
+        with self._lock:
+            self.waiting.extend(par.children)
+            self._wake.notify()
+        return par
+
+    def rescore_async(self, texts: List[str]):
+        """concurrent.futures.Future resolved with the rescoring's dict (requires start())."""
+        fut: Future = Future()
+        self.submit_rescore(texts, future=fut)
+        return fut
+
+    def rescore(self, texts: List[str]) -> Dict[str, Any]:
+        """Language-model scores of the recogniser's alternatives: ``{"scores", "scored_tokens",
+        "common_prefix_tokens", "prompt_tokens", "cached_prefix_tokens", "ms"}``.  ``scores[i]`` is the
+        log-probability, given the ids all alternatives share, that the user's text is exactly
+        ``turn_text(texts[i])``: the sum over the ids after the common prefix plus the turn probe's
+        ``logprob`` (the string closes).  Alternatives that normalise to the same string are scored once
+        and share the value.  The scores of ONE call are comparable with each other and only with each
+        other: another call has another common prefix.  Through the background scheduler when it runs,
+        otherwise by stepping here."""
+        if self._thread is not None:
+            return self.rescore_async(texts).result()
+        r = self.submit_rescore(texts)
+        while not r.done:
+            self.step()
+        if r.error is not None:
+            raise r.error
+        return r.result
+
     def _diagnose(self, batch, toks, logits, n) -> None:
         """A -1 token means no admissible token had a finite logit: record what the row looked like
         (mask population, finite admissible logits) in the request's error for the logs."""
@@ -768,6 +991,8 @@ class LLMIntentEngine:
                "rows_per_iteration": round(self.batch_stats["rows"] / it, 3),
                "samples_per_iteration": round(self.batch_stats["sampled"] / it, 3),
                "grammar_rejects": self.batch_stats.get("rejects", 0),
+               "rescores": self.batch_stats.get("rescores", 0),
+               "rescore_rows": self.batch_stats.get("rescore_rows", 0),
                "host_ms": {k: round(v, 1) for k, v in self.timing.items()}}
         out.update(self.grammar.stats())
         out.update({k: v for k, v in eng.stats.items()})

@@ -1,6 +1,7 @@
 """Brain service: ``GET /health``, ``POST /parse``, ``GET /metrics`` (parity with apps/brain/src/server.ts),
-and ``POST /turn`` and ``POST /summarize``, this project's own: the turn-completion probe and the page
-summary behind the ``summarize`` intent.
+and ``POST /turn``, ``POST /summarize`` and ``POST /rescore``, this project's own: the turn-completion
+probe, the page summary behind the ``summarize`` intent, and the language-model scores of the
+recogniser's n-best alternatives.
 
 Request flow (apps/brain/src/server.ts:89-139):
   ParseRequest validation -> 400 {error:"invalid_request", detail}
@@ -20,6 +21,13 @@ or non-string text, a non-string title or url, or a max_chars that is not an int
 as ``/parse``; 200 {summary, chars, prompt_tokens, cached_prefix_tokens, page_tokens, truncated,
 decode_steps, ms}.  ``/metrics`` counts ``summaries`` and ``summary_tokens`` and gives the mean ``n_kept``
 (ids the nucleus step left per sampled token).
+
+``POST /rescore`` {"alternatives": [1..8 strings]}: 400 {error:"bad_request"} for anything else; 501
+{error:"rescore_unsupported"} for an engine without ``rescore_async`` (keyword, TP); 500 llm_error as
+``/parse``; 200 {scores, scored_tokens, common_prefix_tokens, prompt_tokens, cached_prefix_tokens, ms}
+(LLMIntentEngine.rescore: the scores of one answer are comparable with each other and only with each
+other; a score at -inf is null, JSON has no -inf).  ``/metrics`` counts ``rescore_requests`` and
+observes ``rescore_ms``.
 
 With the LLM engine the grammar makes the first answer schema-valid, so the repair path only
 runs for engines without constrained decoding (or injected faults in tests).
@@ -203,12 +211,45 @@ def build_app(engine: Any = None) -> web.Application:
         m.inc("summarize_ok")
         return web.json_response(out)
 
+    async def rescore(req: web.Request) -> web.Response:
+        """Language-model scores of the recogniser's alternatives (LLMIntentEngine.rescore)."""
+        m: Metrics = app["metrics"]
+        t0 = time.perf_counter()
+        try:
+            body = await req.json()
+        except Exception:  # noqa: BLE001
+            body = None
+        alts = body.get("alternatives") if isinstance(body, dict) else None
+        if not isinstance(alts, list) or not 1 <= len(alts) <= 8 or not all(isinstance(a, str) for a in alts):
+            m.inc("bad_request")
+            return web.json_response({"error": "bad_request",
+                                      "detail": "body must be {\"alternatives\": [1..8 strings]}"}, status=400)
+        eng = app["engine"]
+        if not hasattr(eng, "rescore_async"):
+            m.inc("rescore_unsupported")
+            return web.json_response({"error": "rescore_unsupported"}, status=501)
+        m.inc("rescore_requests")
+        try:
+            # a scheduler engine: the alternatives join the running batch (no serial lock)
+            if hasattr(eng, "start"):
+                eng.start()
+            out = dict(await asyncio.wrap_future(eng.rescore_async(alts)))
+        except Exception as e:  # noqa: BLE001
+            m.inc("llm_error")
+            return web.json_response({"error": "llm_error", "detail": str(e) or e.__class__.__name__}, status=500)
+        # (JSON has no -inf: an alternative the model gives no mass reads null)
+        out["scores"] = [s if isinstance(s, (int, float)) and s == s and abs(s) != float("inf") else None
+                         for s in out.get("scores", [])]
+        m.observe("rescore_ms", (time.perf_counter() - t0) * 1e3)
+        return web.json_response(out)
+
     app.on_cleanup.append(on_cleanup)
     app.router.add_get("/health", health)
     app.router.add_get("/metrics", metrics)
     app.router.add_post("/parse", parse)
     app.router.add_post("/turn", turn)
     app.router.add_post("/summarize", summarize)
+    app.router.add_post("/rescore", rescore)
     return app
 
 

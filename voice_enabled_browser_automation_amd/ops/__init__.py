@@ -1935,6 +1935,84 @@ def set_logprob(logits: torch.Tensor, vocab: int, sets: torch.Tensor, *,
     return out
 
 
+# ----------------------------------------------------------------------------- per-sequence log-probabilities
+RESCORE_MAX_ROWS = 256         # csrc/rescore/rescore.h kRescoreMaxRows: rows per call
+RESCORE_MAX_SEQ = 64           # ... kRescoreMaxSeq: running sums per call
+RESCORE_MAX_VOCAB = 1 << 20    # ... kRescoreMaxVocab
+seq_logprob_launches = 0       # GPU calls of seq_logprob so far (the tests count them)
+
+
+def rescore_ext():
+    """The per-sequence log-probability library ``_vwa_rescore.so`` (loaded once). Raises if unavailable."""
+    return _load_lib("_vwa_rescore", "per-sequence log-probability")
+
+
+def seq_logprob(logits: torch.Tensor, vocab: int, target: torch.Tensor, end_set: torch.Tensor, seq: torch.Tensor,
+                n_seq: int, *, acc_in: Optional[torch.Tensor] = None, lp: Optional[torch.Tensor] = None,
+                acc_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per row of f32 ``logits`` [rows <= 256, >= vocab], the log-probability (softmax over the ids below
+    ``vocab``) of ``target[r]`` -- an id, or -1 for the mass on ``end_set`` (packed allow-bits in the
+    sampler's mask format, int32, >= ceil(vocab / 32) words) -- and, per sequence ``s < n_seq <= 64``,
+    ``acc_out[s] = acc_in[s] + the lp of the rows with seq[r] == s``, added in row order in f32
+    (csrc/rescore/rescore.h has the rules).  ``target``, ``seq`` int32 [rows]; ``acc_in`` f32 [n_seq] or
+    None (zeros); ``lp`` f32 [rows] and ``acc_out`` f32 [n_seq] are allocated when not given.  A row is
+    -inf, never NaN and never above 0, when it cannot be scored (a target outside [-1, vocab), a target
+    column, set or row at -inf); a ``seq[r]`` outside [0, n_seq) adds to nothing.  The sums are
+    comparable only among sequences scored behind the same prefix.  The logits are only read.  One
+    call on the GPU, no host synchronisation; host tensors take the Python reference and never load
+    the library.  Returns ``(lp, acc_out)``."""
+    global seq_logprob_launches
+    i32, f32, dev = torch.int32, torch.float32, logits.device
+    if logits.dim() != 2 or logits.dtype != f32 or logits.stride(1) != 1 \
+            or not (logits.shape[0] == 1 or logits.stride(0) >= logits.shape[1]):
+        raise ValueError(f"seq_logprob: logits must be float32 [>= rows, >= vocab] with contiguous rows that do not "
+                         f"overlap, not {logits.dtype} {tuple(logits.shape)}")
+    if target.dim() != 1 or target.dtype != i32 or not target.is_contiguous() \
+            or not 1 <= target.numel() <= min(RESCORE_MAX_ROWS, logits.shape[0]):
+        raise ValueError(f"seq_logprob: target must be contiguous int32 [1..{min(RESCORE_MAX_ROWS, logits.shape[0])}] "
+                         f"(one per row of the logits), not {target.dtype} {tuple(target.shape)}")
+    rows = target.numel()
+    vocab, n_seq = int(vocab), int(n_seq)
+    if not 1 <= vocab <= min(logits.shape[1], RESCORE_MAX_VOCAB):
+        raise ValueError(f"seq_logprob: vocab = {vocab} outside [1, {min(logits.shape[1], RESCORE_MAX_VOCAB)}] (the "
+                         "logits' row length)")
+    if not 1 <= n_seq <= RESCORE_MAX_SEQ:
+        raise ValueError(f"seq_logprob: n_seq = {n_seq} outside [1, {RESCORE_MAX_SEQ}]")
+    words = (vocab + 31) // 32
+    if end_set.dtype != i32 or not end_set.is_contiguous() or end_set.numel() < words:
+        raise ValueError(f"seq_logprob: end_set must be contiguous int32 with >= {words} words (vocab = {vocab} bits), "
+                         f"not {end_set.dtype} {tuple(end_set.shape)}")
+    if lp is None:
+        lp = torch.empty(rows, dtype=f32, device=dev)
+    if acc_out is None:
+        acc_out = torch.empty(n_seq, dtype=f32, device=dev)
+    for name, t, dt, n in (("seq", seq, i32, rows), ("lp", lp, f32, rows), ("acc_out", acc_out, f32, n_seq),
+                           ("acc_in", acc_in, f32, n_seq)):
+        if t is not None and (t.dim() != 1 or t.dtype != dt or not t.is_contiguous() or t.numel() != n):
+            raise ValueError(f"seq_logprob: {name} must be contiguous {dt} [{n}], not {t.dtype} {tuple(t.shape)}")
+    for name, t in (("target", target), ("end_set", end_set), ("seq", seq), ("acc_in", acc_in), ("lp", lp),
+                    ("acc_out", acc_out)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"seq_logprob: {name} is on {t.device}, the logits on {dev}")
+    ins = [("logits", logits, 4 * ((rows - 1) * logits.stride(0) + vocab)), ("target", target, 4 * rows),
+           ("end_set", end_set, 4 * words), ("seq", seq, 4 * rows)]
+    if acc_in is not None:
+        ins.append(("acc_in", acc_in, 4 * n_seq))
+    outs = [("lp", lp, 4 * rows), ("acc_out", acc_out, 4 * n_seq)]
+    for k, (on, ot, ob) in enumerate(outs):
+        a = ot.data_ptr()
+        for name, t, nb in ins + outs[:k]:
+            b = t.data_ptr()
+            if a < b + nb and b < a + ob:
+                raise ValueError(f"seq_logprob: {on} must not overlap {name}")
+    if not _gpu(logits):
+        return ref.seq_logprob(logits, vocab, target, end_set, seq, n_seq, acc_in, lp, acc_out)
+    # (a missing library raises: there is no other GPU path)
+    rescore_ext().seq_logprob(logits, vocab, target, end_set, seq, n_seq, acc_in, lp, acc_out)
+    seq_logprob_launches += 1
+    return lp, acc_out
+
+
 # ----------------------------------------------------------------------------- nucleus step
 NUCLEUS_MAX_ROWS = 64          # csrc/nucleus/nucleus.h kNucleusMaxRows: rows per launch
 NUCLEUS_MAX_VOCAB = 128256     # ... kNucleusMaxVocab (the Llama-3 vocabulary)

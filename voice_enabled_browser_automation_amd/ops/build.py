@@ -15,6 +15,7 @@ sources           library               what
 ``csrc/turn``     ``_vwa_turn.so``      set log-probability (turn-completion probe)
 ``csrc/nucleus``  ``_vwa_nucleus.so``   repetition penalty, top-k / top-p mask step
 ``csrc/ingest``   ``_vwa_ingest.so``    wire audio: G.711 / PCM16 decode, downmix, resample
+``csrc/rescore``  ``_vwa_rescore.so``   per-sequence log-probabilities (n-best rescoring)
 ================  ====================  ===============================================
 
 Every ``*.hip`` of a library's directory is compiled with ``hipcc --offload-arch=gfx950`` into its
@@ -47,8 +48,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # (source directory under csrc/, extension name); the first row is the main library
 KERNEL_LIBS = (("kernels", "_vwa_kernels"), ("align", "_vwa_align"), ("sot", "_vwa_sot"), ("beam", "_vwa_beam"),
                ("boost", "_vwa_boost"), ("tsrules", "_vwa_tsrules"), ("score", "_vwa_score"), ("turn", "_vwa_turn"),
-               ("nucleus", "_vwa_nucleus"), ("ingest", "_vwa_ingest"))
-KERNEL_SO, ALIGN_SO, SOT_SO, BEAM_SO, BOOST_SO, TSRULES_SO, SCORE_SO, TURN_SO, NUCLEUS_SO, INGEST_SO = (
+               ("nucleus", "_vwa_nucleus"), ("ingest", "_vwa_ingest"), ("rescore", "_vwa_rescore"))
+(KERNEL_SO, ALIGN_SO, SOT_SO, BEAM_SO, BOOST_SO, TSRULES_SO, SCORE_SO, TURN_SO, NUCLEUS_SO, INGEST_SO,
+ RESCORE_SO) = (
     os.path.join(HERE, ext_name + ".so") for _, ext_name in KERNEL_LIBS)
 NATIVE_SO = os.path.join(HERE, "_vwa_native.so")
 # headers any library's sources may include, besides those of its own directory
@@ -148,7 +150,7 @@ def build_native(force: bool = False) -> str:
 
 def build_all(force: bool = False) -> list[str]:
     # the libraries build side by side: the main library's longest source (skinny_stream.hip, all the
-    # chained-layer instantiations in one translation unit) takes minutes on one core, and the nine
+    # chained-layer instantiations in one translation unit) takes minutes on one core, and the ten
     # small libraries and the CPU runtime, a few minutes one after the other, fit beside it
     with cf.ThreadPoolExecutor(max_workers=len(KERNEL_LIBS) + 1) as ex:
         native = ex.submit(build_native, force)

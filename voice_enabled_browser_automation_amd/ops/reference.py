@@ -709,6 +709,37 @@ def set_logprob(logits, vocab, sets, out):
     return out
 
 
+def seq_logprob(logits, vocab, target, end_set, seq, n_seq, acc_in, lp, acc_out):
+    """The per-sequence log-probabilities on host tensors, as csrc/rescore/rescore.h states them: each
+    row's value in f64, rounded to f32 once; the sums as f32 additions in row order."""
+    ninf = float("-inf")
+    ids = torch.arange(vocab)
+    s = end_set.reshape(-1)
+    on = ((s[ids >> 5] >> (ids & 31)) & 1).bool()
+    for r in range(target.numel()):
+        t = int(target[r])
+        val = ninf
+        if -1 <= t < vocab:
+            x = logits[r, :vocab].double()
+            live = x > ninf  # (False for a NaN too)
+            if bool(live.any()):
+                A = float(torch.logsumexp(x[live], 0))
+                if t == -1:
+                    hit = live & on
+                    if bool(hit.any()):
+                        val = min(float(torch.logsumexp(x[hit], 0)) - A, 0.0)
+                elif bool(live[t]):
+                    val = min(float(x[t]) - A, 0.0)
+        lp[r] = val
+    acc = torch.zeros(n_seq, dtype=torch.float32) if acc_in is None else acc_in.clone()
+    for r in range(target.numel()):
+        k = int(seq[r])
+        if 0 <= k < n_seq:
+            acc[k] = acc[k] + lp[r]  # f32 + f32, in row order
+    acc_out.copy_(acc)
+    return lp, acc_out
+
+
 def _pack_bits32(on: torch.Tensor, words: int) -> torch.Tensor:
     """bool [n <= 32 words] -> the sampler's packed allow-bits, int32 [words]."""
     bits = torch.zeros(words * 32, dtype=torch.int64)

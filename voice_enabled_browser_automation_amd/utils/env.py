@@ -109,6 +109,9 @@ class Settings(BaseModel):
     VWA_TURN_URL: Optional[str] = Field(None, description="voice -> brain /turn URL (default: BRAIN_URL with /parse replaced by /turn)")
     VWA_TURN_THRESHOLD: float = Field(0.5, gt=0.0, le=1.0, description="voice: a pending text whose probe answers p_end >= this is a finished command. In (0, 1]; 1.0 never commits early. 0.5 is a policy default and is NOT tuned on real speech or real weights")
     VWA_COMMIT_MIN_MS: float = Field(0.0, ge=0.0, description="voice: silence after the speech end before a command the turn probe judged complete is committed (0: as soon as the verdict and the ASR final are both there)")
+    VWA_RESCORE: bool = Field(False, description="voice: rescore a beam final's n-best alternatives with the brain's language model (POST /rescore) before the text joins the pending command, and take the alternative with the best acoustic + VWA_RESCORE_WEIGHT x language-model score; the recogniser's final events then carry every alternative's logprob. Needs VWA_ASR_BEAM and VWA_ASR_ALTERNATIVES >= 2 (0, the default: no request is ever made to /rescore and every event and frame is what it was)")
+    VWA_RESCORE_URL: Optional[str] = Field(None, description="voice -> brain /rescore URL (default: BRAIN_URL with /parse replaced by /rescore)")
+    VWA_RESCORE_WEIGHT: float = Field(0.5, ge=0.0, description="voice: weight of the language-model score against the recogniser's acoustic sum log-probability in n-best rescoring (0: the recogniser's order stands). >= 0; 0.5 lies in the range n-best rescoring commonly uses and is NOT tuned on real speech or real weights")
     VWA_SUMMARIZE: bool = Field(False, description="executor: the summarize intent reads the page's title, url and visible text and asks the brain (POST /summarize) for a spoken-style summary (0, the default: the step answers the fixed note it always did and no request is made)")
     VWA_SUMMARIZE_URL: Optional[str] = Field(None, description="executor -> brain /summarize URL (default: BRAIN_URL with /parse replaced by /summarize)")
     VWA_SUMMARY_PAGE_CHARS: int = Field(20000, ge=1, description="executor: at most this many characters of the page's visible text are sent to /summarize (the brain cuts further, by tokens, to its context window)")
@@ -189,6 +192,9 @@ class Settings(BaseModel):
         if self.VWA_ASR_ALTERNATIVES > self.VWA_ASR_BEAM:
             raise ValueError(f"VWA_ASR_ALTERNATIVES={self.VWA_ASR_ALTERNATIVES} exceeds VWA_ASR_BEAM={self.VWA_ASR_BEAM}: "
                              "a beam of W hypotheses has no more than W alternatives")
+        if self.VWA_RESCORE and self.VWA_ASR_ALTERNATIVES < 2:
+            raise ValueError("VWA_RESCORE=1 needs alternatives to rescore: set VWA_ASR_BEAM and VWA_ASR_ALTERNATIVES "
+                             f"to 2..8 (VWA_ASR_ALTERNATIVES={self.VWA_ASR_ALTERNATIVES})")
         return self
 
     @classmethod

@@ -13,6 +13,15 @@ Per connection:
     speculative final pass (``VWA_SPEC_BRAIN``), so its latency hides in the endpoint / commit
     wait, and its answer is used only if the committed text is exactly the text it parsed (and
     the context did not change meanwhile) -- otherwise it is dropped and the merged text parsed;
+  * n-best rescoring (``VWA_RESCORE``, off by default): a beam final carries ranked alternatives with
+    their acoustic log-probabilities; before its text joins the pending command the transcripts go to
+    the brain (``POST /rescore``: the language model's log-probability that the user's text is exactly
+    each alternative, behind the same few-shot commands) and the alternative with the best
+    ``logprob + VWA_RESCORE_WEIGHT x score`` is the final's text -- "sort by price", not "sore by
+    price".  The ``transcript_final`` frame is sent first, unchanged; a changed choice is followed by
+    one ``info`` frame ``{"rescored": {"from", "to", "scores"}}``.  Any error, a timeout or a malformed
+    answer keeps the recogniser's first; a 501 ends the asking.  Partials, speculative finals and
+    finals with one alternative never ask;
   * turn-completion probe (``VWA_TURN``, off by default): a fixed silence timer cannot tell "search
     for" + pause from "scroll down" + pause; the brain can (``POST /turn``: the probability that the
     pending text is a finished command).  The connection asks on the speculative final pass and,
@@ -172,7 +181,9 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
               executor_url: Optional[str] = None, debounce_ms: Optional[float] = None,
               commit_ms: Optional[float] = None, spec_brain: Optional[bool] = None, turn: Optional[bool] = None,
               turn_url: Optional[str] = None, turn_threshold: Optional[float] = None,
-              commit_min_ms: Optional[float] = None) -> web.Application:
+              commit_min_ms: Optional[float] = None, rescore: Optional[bool] = None,
+              rescore_url: Optional[str] = None, rescore_weight: Optional[float] = None,
+              rescore_timeout_s: float = 5.0) -> web.Application:
     """asr_factory() -> a StreamingAsrSession-like object (push(bytes)->events, flush()->events);
     None = passthrough mode (no recognizer, as the reference without DEEPGRAM_API_KEY)."""
     app = web.Application()
@@ -208,6 +219,17 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
         raise ValueError(f"commit_min_ms = {commit_min_ms} is negative")
     early_s = max(debounce_ms, commit_min_ms - knob("VWA_ENDPOINT_MS")) / 1000.0
     turn_state = {"unsupported": False}  # set by the brain's first 501: the app stops asking
+    # n-best rescoring (module docstring): off unless VWA_RESCORE
+    rescore_on = bool(knob("VWA_RESCORE") if rescore is None else rescore)
+    if rescore_url is None:
+        rescore_url = knob("VWA_RESCORE_URL")
+    if not rescore_url:
+        base, sep, rest = brain_url.rpartition("/parse")
+        rescore_url = base + "/rescore" + rest if sep else brain_url.rstrip("/") + "/rescore"
+    rescore_weight = float(knob("VWA_RESCORE_WEIGHT") if rescore_weight is None else rescore_weight)
+    if not rescore_weight >= 0.0:
+        raise ValueError(f"rescore_weight = {rescore_weight} is negative")
+    rescore_state = {"unsupported": False}  # likewise
 
     async def on_startup(app_):
         app_["http"] = aiohttp.ClientSession(timeout=aiohttp.ClientTimeout(total=120))
@@ -514,6 +536,58 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
             st["debounce"].cancel()
             start_debounce(max(0.0, st["t_final"] + early_s - time.perf_counter()), early=True)
 
+        async def rescore_final(alts, text: str) -> str:
+            """The text of a beam final after n-best rescoring: the alternative with the best acoustic +
+            weight x language-model score (one /rescore call, NOT under the brain lock: it changes no
+            context).  Ties go to the recogniser's order; an alternative at -inf loses to any finite
+            one; anything but a well-formed answer keeps the recogniser's first."""
+            cands = [a for a in alts if isinstance(a, dict) and isinstance(a.get("transcript"), str)
+                     and isinstance(a.get("logprob"), (int, float)) and not isinstance(a.get("logprob"), bool)]
+            if len(cands) < 2 or cands[0] is not alts[0]:
+                return text
+            m.inc("rescore_asked")
+            t0 = time.perf_counter()
+            lm = None
+            try:
+                async with app["http"].post(rescore_url, json={"alternatives": [a["transcript"] for a in cands]},
+                                            timeout=aiohttp.ClientTimeout(total=rescore_timeout_s)) as resp:
+                    status, body = resp.status, await resp.text()
+                if status == 501:
+                    if not rescore_state["unsupported"]:
+                        rescore_state["unsupported"] = True
+                        print(f"[voice] the brain at {rescore_url} does not rescore (501): VWA_RESCORE is ignored "
+                              "from here on", flush=True)
+                elif status == 200:
+                    sc = json.loads(body).get("scores")
+                    if isinstance(sc, list) and len(sc) == len(cands) and all(
+                            s is None or (isinstance(s, (int, float)) and not isinstance(s, bool) and s == s)
+                            for s in sc):
+                        lm = [float("-inf") if s is None else float(s) for s in sc]
+            except Exception:  # noqa: BLE001  (refused, timed out, not JSON, not an object)
+                pass
+            if lm is None:
+                m.inc("rescore_failed")
+                return text
+            m.observe("rescore_ms", (time.perf_counter() - t0) * 1e3)
+            ninf = float("-inf")
+            totals = []
+            for a, s in zip(cands, lm):
+                ac = float(a["logprob"])
+                # (never NaN: an infinite term decides before the weight, which may be 0, multiplies it)
+                totals.append(ninf if not (s > ninf and ac > ninf) else
+                              (ac + rescore_weight * s if s < float("inf") and ac < float("inf") else float("inf")))
+            best = 0
+            for i, t in enumerate(totals):
+                if t > totals[best]:
+                    best = i
+            chosen = cands[best]["transcript"].strip()
+            if best == 0 or not chosen or chosen == text:
+                return text
+            m.inc("rescore_changed")
+            await send({"type": "info", "payload": {"rescored": {
+                "from": text, "to": chosen, "scores": [t if abs(t) != float("inf") else None for t in totals]}}})
+            return chosen
+
         def on_speculative_final(text: str):
             """The ASR's speculative final pass finished (the user has been silent for
             VWA_SPEC_FINAL_MS): parse pending + it now, commit later (process); with VWA_TURN, ask
@@ -552,6 +626,9 @@ def build_app(asr_factory: Optional[Callable[[], Any]] = None, *, brain_url: Opt
                 st["t_final"] = time.perf_counter()
                 if st["t_utt"] is not None:
                     m.observe("speech_to_final_ms", (st["t_final"] - st["t_utt"]) * 1e3)
+                if rescore_on and not rescore_state["unsupported"]:
+                    # (the frame above went out in the recogniser's order; only the command's text changes)
+                    text = await rescore_final((ev.get("channel") or {}).get("alternatives") or [], text)
                 st["pending"] = f"{st['pending']} {text}" if st["pending"] else text
                 if st["debounce"] is not None:
                     st["debounce"].cancel()
